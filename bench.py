@@ -8,9 +8,14 @@ iterations (forward, L1, backward, Adam) and the prune.  The loop is driven thro
 C++ host layer: createTsdfEngine(DatasetReader, config) -> CLIEngine -> SLAMPipeline::setTsdfEngine -> one processFrame per
 step (gps_slam_amd/host/infinitam_tools.hpp, slam_pipeline.hpp).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1: launched by torch.distributed.run, one rank per GPU, each rank runs an INDEPENDENT scene (different seed) -> weak
 scaling, no data-path collective; barrier + max-over-ranks timing only.
+
+A plain run does only what the headline needs: set-up, prologue + warm-up, ONE window of exactly K timed steps of the overlap
+schedule, the outputs of its last step when --dump-outputs is given, and the result line.  --full adds everything else as
+before: both schedules, --windows windows each (default 5; `value` = the median window), the in-loop kernel window, the roofline,
+render PSNR against the oracle, the whole-run / workload / other-configuration legs, the CPU baseline and bench_full.json.
 
 Timed window.  The map update of a keyframe (every 10th frame) is ~10 frames' worth of GPU work; a window that cuts a
 keyframe period in the middle measures a different mix for every (K, W), and the first update of a freshly seeded scene is
@@ -224,8 +229,40 @@ class Scene:
         if trace:
             sys.stderr.write("flush: %.3f ms\n" % (1e3 * (time.perf_counter() - t)))
 
+    def outputs(self, max_gaussians=1 << 16, seed=0):
+        """What a caller of the loop holds after the last processed frame, as float32 numpy arrays: the estimated camera pose
+        (c2w), the live raycast of the TSDF from it (vertex map, H x W x 4) and the Gaussian map.  A map of more than
+        max_gaussians rows is reduced to a fixed, seeded sample of rows (gaussian_rows holds their indices, gaussian_count
+        the map's size, both float64)."""
+        self.pipe.flush()
+        torch.cuda.synchronize()
+        W, H = self.cams[0].width, self.cams[0].height
+        out = {"pose_c2w": self.engine.lastPose()[1].reshape(4, 4).T.contiguous(),   # invM, column-major -> c2w
+               "live_vertex": self.engine.GetLiveVertex().view(torch.float32).reshape(H, W, 4)}
+        P = self.model.getGaussianParms()
+        n = int(P.getGaussianNum())
+        rows = np.arange(n) if n <= max_gaussians else np.sort(np.random.default_rng(seed).choice(n, max_gaussians, replace=False))
+        idx = torch.as_tensor(rows, dtype=torch.int64)
+        for name, get in (("means", P.getMeans), ("scales", P.getScales), ("quats", P.getQuats), ("features_dc", P.getFeaturesDc),
+                          ("features_rest", P.getFeaturesRest), ("opacities", P.getOpacities)):
+            t = get()
+            out["gaussian_" + name] = t[idx.to(t.device)].reshape(len(rows), -1)
+        out["gaussian_rows"] = torch.as_tensor(rows, dtype=torch.float64)
+        out["gaussian_count"] = torch.tensor([n], dtype=torch.float64)
+        return {k: v.detach().cpu().numpy() if v.dtype == torch.float64 else v.detach().float().cpu().numpy() for k, v in out.items()}
+
     def close(self):
         self.cli.Shutdown()
+
+
+def dump_outputs(arrays, out_dir, limit_bytes=64 << 20):
+    """arrays (name -> float32 / float64 numpy array) as out_dir/<name>.npy"""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= limit_bytes, "outputs are %d bytes (> %d)" % (total, limit_bytes)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def prime(device):
@@ -311,11 +348,19 @@ def main(argv=None, scene_factory=None, backend="nccl", need_gpu=True, extras=Tr
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (both schedules, 5 windows each, in-loop kernel window, "
+                         "roofline, PSNR against the oracle, whole-run / workload / other-configuration legs, CPU baseline, "
+                         "bench_full.json); a plain run times one window of --steps steps of the overlap schedule")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left to a caller (tracked pose, live raycast, "
+                         "Gaussian map; Scene.outputs) as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None,
                     help="consecutive K-step windows timed per schedule (each bracketed by barrier + synchronize, max over ranks); "
-                         "`value` is the MEDIAN window, config.windows_ms_per_step lists all of them")
-    ap.add_argument("--schedule", choices=("both", "overlap", "sequential"), default="both",
-                    help="which keyframe schedule(s) to time; `value` is the overlap schedule unless only sequential is run")
+                         "`value` is the MEDIAN window, config.windows_ms_per_step lists all of them (default 1, 5 with --full)")
+    ap.add_argument("--schedule", choices=("both", "overlap", "sequential"), default=None,
+                    help="which keyframe schedule(s) to time; `value` is the overlap schedule unless only sequential is run "
+                         "(default overlap, both with --full)")
     ap.add_argument("--gaussians", type=int, default=200000)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
@@ -342,6 +387,11 @@ def main(argv=None, scene_factory=None, backend="nccl", need_gpu=True, extras=Tr
                          "depth-only ExtendedTracker estimates the pose of every frame, as BASELINE configs[2] "
                          "(\"full track + TSDF + Gaussian optimize\") describes")
     args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if args.schedule is None:
+        args.schedule = "both" if args.full else "overlap"
+    extras = extras and args.full
 
     from gps_slam_amd.dist_util import scene_seed
     rank, local_rank, world, grp, placement, device = setup_ranks(backend=backend, need_gpu=need_gpu)
@@ -366,6 +416,7 @@ def main(argv=None, scene_factory=None, backend="nccl", need_gpu=True, extras=Tr
                                               keyframe_theta=args.keyframe_theta, keyframe_trans=args.keyframe_trans)
 
     schedules = ("sequential", "overlap") if args.schedule == "both" else (args.schedule,)
+    main_sched = "overlap" if "overlap" in schedules else schedules[0]
     results, scene = {}, None
     for sched in schedules:
         if scene is not None:
@@ -401,17 +452,18 @@ def main(argv=None, scene_factory=None, backend="nccl", need_gpu=True, extras=Tr
         order = sorted(range(NW), key=lambda i: windows[i]["seconds"])
         med = windows[order[NW // 2]]  # the median window (upper median for an even count): every reported number is of ONE window
         ms = [w["ms_per_step"] for w in windows]
+        if args.dump_outputs and rank == 0 and sched == main_sched:   # (before the in-loop window moves the scene on)
+            dump_outputs(scene.outputs(), args.dump_outputs)
         if in_loop and rank == 0:
             from bench_kernels import in_loop_kernel_times
             lo = first + NW * K
             marker()   # (the in-loop window between its own pair of phase markers: tools/prof_summary.py tabulates it separately)
-            med = dict(med, schedule=sched, in_loop=in_loop_kernel_times(lambda: scene.run(lo, lo + K), K))
+            med = dict(med, schedule=sched, in_loop=in_loop_kernel_times(lambda a, b: scene.run(lo + a, lo + b), K))
             marker()
             dev_sync()
         results[sched] = dict(med, windows_ms_per_step=ms, window_spread=(max(ms) - min(ms)) / med["ms_per_step"],
                               window_spread_detrended=_detrended_spread(ms), windows_gaussians=[w["gaussians"] for w in windows],
                               windows_device_mallocs=[w["device_mallocs"] for w in windows])
-    main_sched = "overlap" if "overlap" in results else schedules[0]
     dt = results[main_sched]["seconds"]
 
     if rank == 0:
@@ -434,7 +486,8 @@ def main(argv=None, scene_factory=None, backend="nccl", need_gpu=True, extras=Tr
                        "schedules": {k: {kk: vv for kk, vv in v.items() if kk != "seconds"} for k, v in results.items()},
                        "stats": results[main_sched]["stats"], "placement": placement},
         }
-        flat = {"keyframe_theta_deg": args.keyframe_theta, "keyframe_trans_m": args.keyframe_trans, "env_overrides": env_overrides()}
+        flat = {"keyframe_theta_deg": args.keyframe_theta, "keyframe_trans_m": args.keyframe_trans, "env_overrides": env_overrides(),
+                "full": bool(args.full)}
         if "sequential" in results:
             flat["sequential_fps"] = world * K / results["sequential"]["seconds"]
         if "overlap" in results:
@@ -521,7 +574,7 @@ def main(argv=None, scene_factory=None, backend="nccl", need_gpu=True, extras=Tr
         # (the reference's own whole-run FPS, the sequential schedule, the other single-GPU configurations, the keyframe
         # thresholds, the frame / iteration HBM fractions, which A/B switches were set) is one of them
         out["config"] = dict(flat, **out["config"])
-        emit(out, full_line=args.full_line, side_dir=os.environ.get("GPS_BENCH_SIDE_DIR"))
+        emit(out, full_line=args.full_line, side_dir=os.environ.get("GPS_BENCH_SIDE_DIR"), write_full=args.full)
     # ranks != 0 wait here while rank 0 runs its post-window measurements and prints: no rank tears the process group down
     # (or exits, which torch.distributed.run treats as the job ending) under another rank's feet
     grp.barrier()
@@ -553,7 +606,7 @@ def _sig(v, digits=6):
     return v
 
 
-def compact_line(out):
+def compact_line(out, full_record=True):
     """The stdout line of the contract, <= LINE_LIMIT bytes: the headline fields, `config` = workload + the flat scalars (the
     reference's own whole-run FPS, both schedules, the other single-GPU configurations, thresholds, A/B switches), `roofline` =
     the dominant kernel's in-loop figures + the frame / iteration fractions, `cpu_baseline` = the reference CPU engine's rate.
@@ -569,7 +622,8 @@ def compact_line(out):
     for k in ("render_psnr_db_vs_input", "tsdf_colour_psnr_db_vs_input", "render_psnr_db_vs_oracle"):
         if isinstance(q.get(k), (int, float)):
             c[k] = _sig(float(q[k]), 5)
-    c["full_record"] = "bench_full.json"
+    if full_record:
+        c["full_record"] = "bench_full.json"
     line["config"] = c
     r = out.get("roofline")
     if r:
@@ -587,13 +641,13 @@ def compact_line(out):
     return line
 
 
-def emit(out, full_line=False, side_dir=None):
+def emit(out, full_line=False, side_dir=None, write_full=True):
     """rank 0: the full record to bench_full.json (beside this file; also under gpurun_out/ when that exists, so that a gpurun
     call brings it back), ONE compact JSON line to stdout as the last thing printed there"""
     _finite(out)
     full = json.dumps(out, allow_nan=False)
     for d in ([side_dir] if side_dir else [ROOT, os.path.join(ROOT, "gpurun_out")]):
-        if os.path.isdir(d):
+        if write_full and os.path.isdir(d):
             try:
                 with open(os.path.join(d, "bench_full.json"), "w") as f:
                     f.write(full + "\n")
@@ -601,8 +655,9 @@ def emit(out, full_line=False, side_dir=None):
                 print("bench_full.json not written in %s: %s" % (d, e), file=sys.stderr)
     # (the full record is NOT echoed to stderr: a driver that captures stdout and stderr into one buffer would then see a 20+ KB
     # line next to -- possibly after -- the compact one)
-    print("bench: full record (%d bytes) in bench_full.json" % len(full), file=sys.stderr, flush=True)
-    text = full if full_line else json.dumps(compact_line(out), allow_nan=False, separators=(",", ":"))
+    if write_full:
+        print("bench: full record (%d bytes) in bench_full.json" % len(full), file=sys.stderr, flush=True)
+    text = full if full_line else json.dumps(compact_line(out, full_record=write_full), allow_nan=False, separators=(",", ":"))
     assert full_line or len(text.encode()) <= LINE_LIMIT, "compact line is %d bytes (> %d)" % (len(text.encode()), LINE_LIMIT)
     sys.stdout.flush()
     print(text, flush=True)

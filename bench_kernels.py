@@ -25,34 +25,42 @@ TIMED_KINDS = ("preprocess_bwd_kernel", "preprocess_fwd_kernel", "raster_ges_fwd
                "sb_scan_kernel", "sb_scatter_kernel", "integrate_kernel", "raycast_kernel")   # == GPS_TIMED_* (include/gps_slam_hip.h)
 
 
-def in_loop_kernel_times(run, frames):
-    """Per-kernel launch durations INSIDE the running schedule: gps_launch_timing_start, `run()` (K SLAM frames of the scene the
-    timed windows just measured, same schedule, same streams and host threads), gps_launch_timing_stop.  Every launch of the
-    instrumented kernels stamps the device's 100 MHz wall clock at the start and end of each of its waves into its workgroup's
-    {first start, last end} slot (csrc/launch_timing.hpp: the kernel's own execution interval -- a rocprofv3 kernel trace reports the
-    same launches 1-3 us longer, the dispatch's ramp-up and the end-of-kernel release); this is what the `roofline` of the
-    line is priced with -- the kernels-alone micro-loops of roofline_section run with nothing beside them and warm
-    inputs.  The window is an extra one after the timed windows."""
+def in_loop_kernel_times(run, frames, chunk=20):
+    """Per-kernel launch durations INSIDE the running schedule: gps_launch_timing_start, `run(a, b)` (frames a..b-1 of a K-frame
+    window of the scene the timed windows just measured, same schedule, same streams and host threads), gps_launch_timing_stop.
+    Every launch of the instrumented kernels stamps the device's 100 MHz wall clock at the start and end of each of its waves into
+    its workgroup's {first start, last end} slot (csrc/launch_timing.hpp: the kernel's own execution interval -- a rocprofv3 kernel
+    trace reports the same launches 1-3 us longer, the dispatch's ramp-up and the end-of-kernel release); this is what the
+    `roofline` of the line is priced with -- the kernels-alone micro-loops of roofline_section run with nothing beside them and
+    warm inputs.  The window is an extra one after the timed windows.  The slot ring holds ~20 frames' workgroups, so a longer
+    window is stamped `chunk` frames at a time (one start / stop each) and the per-kernel totals are summed over the chunks."""
     from gps_slam_amd._lib import lib
-    assert lib.gps_launch_timing_start(1 << 21) == 0   # workgroup slots (32 MB): ~0.4 M workgroups in 20 frames
-    t0 = time.perf_counter()
-    try:
-        run()
-        torch.cuda.synchronize()
-    finally:
-        rc = lib.gps_launch_timing_stop()
-    wall = time.perf_counter() - t0
-    assert rc == 0, "gps_launch_timing_stop: %d" % rc
+    acc = [[0.0, 0, 0.0, 0, 0.0] for _ in TIMED_KINDS]   # total us, launches, flagged total us, flagged launches, max us
+    wall = 0.0
+    for a in range(0, frames, chunk):
+        b = min(frames, a + chunk)
+        assert lib.gps_launch_timing_start(1 << 21) == 0   # workgroup slots (32 MB): ~0.4 M workgroups in 20 frames
+        t0 = time.perf_counter()
+        try:
+            run(a, b)
+            torch.cuda.synchronize()
+        finally:
+            rc = lib.gps_launch_timing_stop()
+        wall += time.perf_counter() - t0
+        assert rc == 0, "gps_launch_timing_stop: %d" % rc
+        for kind in range(len(TIMED_KINDS)):
+            tot, totf, mx = C.c_double(), C.c_double(), C.c_double()
+            n, nf, dropped = C.c_int64(), C.c_int64(), C.c_int64()
+            assert lib.gps_launch_timing_read(kind, C.byref(tot), C.byref(n), C.byref(totf), C.byref(nf), C.byref(mx), C.byref(dropped)) == 0
+            assert dropped.value == 0, "launch timing ring overflowed"
+            s_ = acc[kind]
+            s_[0] += tot.value; s_[1] += n.value; s_[2] += totf.value; s_[3] += nf.value; s_[4] = max(s_[4], mx.value)
     out = {"frames": frames, "window_ms_per_step": 1e3 * wall / frames, "kernels": {}}
-    for kind, name in enumerate(TIMED_KINDS):
-        tot, totf, mx = C.c_double(), C.c_double(), C.c_double()
-        n, nf, dropped = C.c_int64(), C.c_int64(), C.c_int64()
-        assert lib.gps_launch_timing_read(kind, C.byref(tot), C.byref(n), C.byref(totf), C.byref(nf), C.byref(mx), C.byref(dropped)) == 0
-        assert dropped.value == 0, "launch timing ring overflowed"
-        if n.value:
-            out["kernels"][name] = {"launches": n.value, "avg_us": tot.value / n.value, "us_per_frame": tot.value / frames, "max_us": mx.value,
-                                    "launches_flagged": nf.value, "avg_us_flagged": totf.value / nf.value if nf.value else None,
-                                    "avg_us_unflagged": (tot.value - totf.value) / (n.value - nf.value) if n.value > nf.value else None}
+    for (tot, n, totf, nf, mx), name in zip(acc, TIMED_KINDS):
+        if n:
+            out["kernels"][name] = {"launches": n, "avg_us": tot / n, "us_per_frame": tot / frames, "max_us": mx,
+                                    "launches_flagged": nf, "avg_us_flagged": totf / nf if nf else None,
+                                    "avg_us_unflagged": (tot - totf) / (n - nf) if n > nf else None}
     return out
 
 

@@ -173,11 +173,15 @@ class _StubScene:
         self.pipe.n["opt_iters"] += 2 * (hi - lo)
         self.cli.uploadedBytes += 6 * 64 * 48 * (hi - lo)
 
+    def outputs(self):
+        import numpy as np
+        return {"frames": np.asarray([self.pipe.n["frames"]], np.float64), "pose_c2w": np.eye(4, dtype=np.float32)}
+
     def close(self):
         pass
 
 
-def _main_worker(rank, world, port, out_dir):
+def _main_worker(rank, world, port, out_dir, argv=("--full", "--windows", "3")):
     import contextlib
     import io
     import json
@@ -192,7 +196,7 @@ def _main_worker(rank, world, port, out_dir):
         return scenes[-1]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "10", "--warmup", "5", "--windows", "3"], scene_factory=factory, backend="gloo",
+        bench.main(["--gpus", str(world), "--steps", "10", "--warmup", "5"] + list(argv), scene_factory=factory, backend="gloo",
                    need_gpu=False, extras=False)
     with open(os.path.join(out_dir, "rank%d.json" % rank), "w") as f:
         json.dump({"stdout": buf.getvalue(), "log": [s.log for s in scenes], "overlap": [s.overlap for s in scenes]}, f)
@@ -271,6 +275,38 @@ def test_bench_main_end_to_end_on_gloo(tmp_path, world):
         assert r["log"] == [[[0, 30], [30, 40], [40, 50], [50, 60]]] * 2
 
 
+def test_bench_main_plain_run_times_exactly_the_steps(tmp_path):
+    """A plain run (no --full): prologue + warm-up, then ONE window of exactly --steps steps of the overlap schedule and nothing
+    else; the line carries ms_per_step of that window, no bench_full.json is written, and --dump-outputs writes the arrays the
+    scene returns for its last step as DIR/<name>.npy."""
+    import json
+    import numpy as np
+    world = 2
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    dump = str(tmp_path / "dump")
+    ps = [ctx.Process(target=_main_worker, args=(r, world, port, str(tmp_path), ("--dump-outputs", dump))) for r in range(world)]
+    for p in ps:
+        p.start()
+    for p in ps:
+        p.join(240)
+        assert p.exitcode == 0
+    res = [json.load(open(tmp_path / ("rank%d.json" % r))) for r in range(world)]
+    lines = [l for l in res[0]["stdout"].splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{")
+    line = json.loads(lines[0], parse_constant=_reject_constant)
+    assert line["steps"] == 10 and line["warmup"] == 5 and line["config"]["windows"] == 1 and line["config"]["full"] is False
+    assert line["config"]["schedule"] == "overlap" and "full_record" not in line["config"] and "roofline" not in line
+    assert abs(line["value"] - world * 10 / (line["ms_per_step"] * 1e-3 * 10)) < 1e-4 * line["value"]
+    for r in res:
+        assert r["overlap"] == [True]
+        assert r["log"] == [[[0, 30], [30, 40]]]
+    assert not any(os.path.exists(tmp_path / ("side%d" % r) / "bench_full.json") for r in range(world))
+    assert sorted(os.listdir(dump)) == ["frames.npy", "pose_c2w.npy"]
+    assert np.load(os.path.join(dump, "frames.npy")).tolist() == [40.0]
+    assert np.load(os.path.join(dump, "pose_c2w.npy")).dtype == np.float32
+
+
 def test_timed_window_is_whole_keyframe_periods():
     import bench
     for w in (0, 5, 10, 20, 25, 31, 40):
@@ -328,3 +364,55 @@ def test_cap_host_threads_respects_the_container_quota(monkeypatch):
     finally:
         monkeypatch.undo()
         torch.set_num_threads(before)
+
+
+def test_in_loop_window_is_stamped_in_bounded_chunks(monkeypatch):
+    """bench_kernels.in_loop_kernel_times: the launch-timing slot ring holds ~20 frames' workgroups, so a K-frame window is stamped
+    20 frames at a time (one start / stop each, every frame of the window covered once) and the per-kernel totals are summed;
+    a chunk that overflows the ring is an error, never a silently short average."""
+    import ctypes as C
+    import bench_kernels
+    from gps_slam_amd import _lib
+
+    class FakeLib:
+        def __init__(self):
+            self.calls, self.live, self.frames = [], False, 0
+
+        def gps_launch_timing_start(self, capacity):
+            assert not self.live
+            self.calls.append("start")
+            self.live, self.frames = True, 0
+            return 0
+
+        def gps_launch_timing_stop(self):
+            self.calls.append("stop")
+            self.live = False
+            return 0
+
+        def gps_launch_timing_read(self, kind, tot, n, totf, nf, mx, dropped):
+            f = self.frames   # every kernel: 2 launches per frame of 10 us (kind 0: one of them flagged, 30 us), max = 10 x frames
+            C.cast(n, C.POINTER(C.c_int64))[0] = 2 * f
+            C.cast(tot, C.POINTER(C.c_double))[0] = (40.0 if kind == 0 else 20.0) * f
+            C.cast(nf, C.POINTER(C.c_int64))[0] = f if kind == 0 else 0
+            C.cast(totf, C.POINTER(C.c_double))[0] = 30.0 * f if kind == 0 else 0.0
+            C.cast(mx, C.POINTER(C.c_double))[0] = 10.0 * f
+            C.cast(dropped, C.POINTER(C.c_int64))[0] = 1 if f > 20 else 0
+            return 0
+
+    fake = FakeLib()
+    monkeypatch.setattr(_lib, "lib", fake)
+    monkeypatch.setattr(bench_kernels.torch.cuda, "synchronize", lambda: None)
+    ran = []
+
+    def run(a, b):
+        assert fake.live
+        ran.append((a, b))
+        fake.frames += b - a
+
+    out = bench_kernels.in_loop_kernel_times(run, 45)
+    assert ran == [(0, 20), (20, 40), (40, 45)] and fake.calls == ["start", "stop"] * 3
+    k0, k1 = out["kernels"]["preprocess_bwd_kernel"], out["kernels"]["raycast_kernel"]
+    assert out["frames"] == 45 and k0["launches"] == 90 and k0["launches_flagged"] == 45 and k0["max_us"] == 200.0
+    assert k0["us_per_frame"] == 40.0 and k0["avg_us_flagged"] == 30.0 and k0["avg_us_unflagged"] == 10.0 and k1["avg_us"] == 10.0
+    with pytest.raises(AssertionError, match="overflowed"):
+        bench_kernels.in_loop_kernel_times(run, 45, chunk=45)

@@ -1,6 +1,6 @@
 # ATen / runtime kernels inside the last timed window of a short sequential bench run: gpurun -- bash tools/probe/aten_names.sh
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf /tmp/an && rocprofv3 --kernel-trace -d /tmp/an -o a -- python bench.py --steps 20 --warmup 5 --windows 2 --schedule sequential --no-cpu-baseline --no-oracle-psnr --no-other-configs --whole-run-frames 0 > /dev/null 2>&1
+rm -rf /tmp/an && rocprofv3 --kernel-trace -d /tmp/an -o a -- python bench.py --full --steps 20 --warmup 5 --windows 2 --schedule sequential --no-cpu-baseline --no-oracle-psnr --no-other-configs --whole-run-frames 0 > /dev/null 2>&1
 python - <<'PY'
 import glob, sqlite3, collections
 db = sqlite3.connect(glob.glob("/tmp/an/**/*.db", recursive=True)[0])

@@ -5,7 +5,7 @@
 # run ON the GPU box:  bash tools/probe/outliers.sh   -> gpurun_out/outliers_*.txt
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
-CMD="python bench.py --steps 20 --warmup 5 --windows 2 --no-cpu-baseline --no-oracle-psnr --no-other-configs"
+CMD="python bench.py --full --steps 20 --warmup 5 --windows 2 --no-cpu-baseline --no-oracle-psnr --no-other-configs"
 rm -rf /tmp/prof_outl && rocprofv3 --kernel-trace -d /tmp/prof_outl -o t -- $CMD > gpurun_out/outliers_bench.log 2>&1
 DB=$(find /tmp/prof_outl -name '*.db' | head -1)
 python tools/outlier_overlap.py "$DB" 2.0 > gpurun_out/outliers_overlap.txt 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # which hardware queue did every chain of the overlap whole-run get?  (kernels.queue_id of a rocprofv3 kernel trace of bench.py)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-rm -rf /tmp/prof_q && rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/prof_q -o q -- python bench.py --no-cpu-baseline --no-oracle-psnr $1 > /tmp/q.log 2>&1
+rm -rf /tmp/prof_q && rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/prof_q -o q -- python bench.py --full --no-cpu-baseline --no-oracle-psnr $1 > /tmp/q.log 2>&1
 grep '^{"metric"' /tmp/q.log | python -c "
 import sys, json
 j=json.loads(sys.stdin.readline()); w=j['config']['whole_run']

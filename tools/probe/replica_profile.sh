@@ -4,7 +4,7 @@
 TAG=${1:-rXX}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
-CMD="python bench.py --width 1200 --height 680 --gaussians 300000 --steps 20 --warmup 5 --windows 3 --no-cpu-baseline --no-oracle-psnr --no-other-configs --whole-run-frames 0"
+CMD="python bench.py --full --width 1200 --height 680 --gaussians 300000 --steps 20 --warmup 5 --windows 3 --no-cpu-baseline --no-oracle-psnr --no-other-configs --whole-run-frames 0"
 rm -rf /tmp/prof_rep && rocprofv3 --kernel-trace --stats -d /tmp/prof_rep -o bench -- $CMD > gpurun_out/replica_prof.log 2>&1
 {
   echo "# $TAG -- Replica-native geometry (1200x680, f = 600), rocprofv3 --kernel-trace --stats summary (MI355X)"

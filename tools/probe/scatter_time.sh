@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 cp gps_slam_amd/libgpsslam_hip.so /tmp/libgps_default.so
 for v in "$@"; do
   if [ "$v" = default ]; then cp /tmp/libgps_default.so gps_slam_amd/libgpsslam_hip.so; else cp tools/probe/libs/libgps_$v.so gps_slam_amd/libgpsslam_hip.so; fi
-  rm -rf /tmp/prof_sc && rocprofv3 --kernel-trace -d /tmp/prof_sc -o s -- python bench.py --width ${W:-1200} --height ${H:-680} --gaussians ${NG:-300000} --steps 20 --warmup 5 --windows 2 --schedule sequential --no-cpu-baseline --no-oracle-psnr --no-other-configs --whole-run-frames 0 > /tmp/sc.log 2>&1
+  rm -rf /tmp/prof_sc && rocprofv3 --kernel-trace -d /tmp/prof_sc -o s -- python bench.py --full --width ${W:-1200} --height ${H:-680} --gaussians ${NG:-300000} --steps 20 --warmup 5 --windows 2 --schedule sequential --no-cpu-baseline --no-oracle-psnr --no-other-configs --whole-run-frames 0 > /tmp/sc.log 2>&1
   python - <<PY
 import glob, sqlite3
 db = sqlite3.connect(glob.glob("/tmp/prof_sc/**/*.db", recursive=True)[0])
