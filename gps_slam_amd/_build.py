@@ -34,7 +34,7 @@ def _stale(target, deps):
 
 
 def build(verbose=False, force=False):
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "gps_slam_hip.h"))
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)

@@ -105,6 +105,7 @@ struct ZeroGrads { float *v_means2d, *v_conics, *v_colors, *v_opacities; };
 
 // compose + L1 (gps_compose_l1) as the epilogue of the forward rasterizer (base_color == nullptr: off): a tile's finished
 // pixels go straight from registers into rgb / loss / the two image gradients -- no launch, no re-read of the render
+struct FwdExposure;   // splat_exposure.hpp
 struct FwdCompose {
     const float* base_color;  // [P,3]
     const float* gt_rgb;      // [P,3]
@@ -118,7 +119,8 @@ struct FwdCompose {
 // splat_raster.hip
 int raster_ges_fwd_rec_launch(int N, const float* records, const float* ref_depth_map, int width, int height,
                               const int32_t* tile_offsets, const int32_t* flatten_ids, const int64_t* counts, float delta_depth,
-                              float* render_colors, float* render_alphas, const FwdCompose* compose, gps_stream stream, const int32_t* tile_order = nullptr);
+                              float* render_colors, float* render_alphas, const FwdCompose* compose, gps_stream stream, const int32_t* tile_order = nullptr,
+                              const FwdExposure* exposure = nullptr);   // exposure: the train step's exposure instance (compose != NULL)
 // gps_raster_ges_bwd_gs with zero_mode: 0 zero-fill here, 1 accumulate onto the buffers, 2 the buffers are already zero
 int raster_ges_bwd_gs_launch(int N, const float* means2d, const float* conics, const float* colors, const float* opacities,
                              const int32_t* radii, const float* ref_depth_map, int width, int height,

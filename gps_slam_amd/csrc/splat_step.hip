@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "splat_adam.hpp"
 #include "splat_bin.hpp"
+#include "splat_exposure.hpp"
 
 extern "C" {
 
@@ -21,7 +22,7 @@ static bool strips_on(const gps_splat_step* a) {
 // along in those kernels (nullptr: the plain render; zero != nullptr also marks a train step: the binning then writes the
 // backward's class lists)
 static int render_chain(const gps_splat_step* a, const gps::FwdCompose* compose, const gps::ZeroGrads* zero, gps_stream stream,
-                        bool preprocessed = false) {
+                        bool preprocessed = false, const gps::FwdExposure* exposure = nullptr) {
     GPS_REQUIRE(a != nullptr);
     const int tw = gps_div_up(a->width, 16), th = gps_div_up(a->height, 16);
     int r;
@@ -57,7 +58,7 @@ static int render_chain(const gps_splat_step* a, const gps::FwdCompose* compose,
                                            compose, stream,
                                            // longest lists first when the map kernels run alone (iteration 257 -> 248 us); beside a
                                            // frame chain row-major order is the better one (overlap 1,285 vs 1,276 frames/s, 6 + 6 runs)
-                                           sb && !gps::map_runs_beside_frame_chain() ? cnt.sb.tile_order : nullptr);
+                                           sb && !gps::map_runs_beside_frame_chain() ? cnt.sb.tile_order : nullptr, exposure);
     else
         r = gps_raster_ges_fwd(a->N, a->means2d, a->conics, a->colors, a->opacities, a->ref_depth_clamped, a->width,
                                a->height, 16, a->tile_offsets, a->flatten_ids, a->counts, a->delta_depth,
@@ -104,11 +105,28 @@ int gps_splat_train_step(const gps_splat_step* a, int adam_step, gps_stream stre
     gps::ZeroGrads no_zero = {};
     GPS_REQUIRE(!a->preprocessed || gps_splat_can_prefetch(a));
     GPS_REQUIRE(!a->next_viewmat || (a->next_Kmat && a->next_cam_pos && gps_splat_can_prefetch(a)));
-    int r = render_chain(a, fused_fwd ? &fc : nullptr, strips ? &no_zero : &zg, stream, a->preprocessed != 0);
+    // per-frame exposure: the camera has a row in the table -> the rasterizer's exposure instance + one reduce / Adam launch below
+    const bool expo = a->exposure && a->exposure_row >= 0 && a->exposure_row < a->exposure_rows;
+    gps::FwdExposure ex = {};
+    if (expo) {
+        GPS_REQUIRE(fused_fwd && a->exposure_grad && a->exposure_m && a->exposure_v && a->exposure_slab && a->exposure_step >= 1);
+        ex = {a->exposure + 12 * (size_t)a->exposure_row, a->exposure_slab};
+    }
+    int r = render_chain(a, fused_fwd ? &fc : nullptr, strips ? &no_zero : &zg, stream, a->preprocessed != 0, expo ? &ex : nullptr);
     if (r != GPS_OK) return r;
     if (!fused_fwd) {
         r = gps_compose_l1(a->width, a->height, a->render_colors, a->weight_sum, a->base_color, nullptr, a->gt_rgb, a->rgb,
                            nullptr, a->loss, a->v_render_colors, a->v_render_alphas, stream);
+        if (r != GPS_OK) return r;
+    }
+    if (expo) {
+        // The table's gradient + Adam step: one single-workgroup launch right behind the forward (it only needs the slab the forward
+        // wrote).  Folding it into a later launch would put a dependent tail into the default instances of the backward kernels
+        // (changing their code) for 12 x rows floats of work; as a launch of its own it leaves every default kernel as it is.
+        const gps::AdamScalars es = gps::adam_scalars(a->exposure_lr, a->beta1, a->beta2, a->adam_eps, a->exposure_step);
+        const int tiles = gps_div_up(a->width, 16) * gps_div_up(a->height, 16);
+        r = gps::exposure_reduce_launch(a->exposure_slab, tiles, a->exposure_rows, a->exposure_row, a->exposure_grad, a->exposure,
+                                        a->exposure_m, a->exposure_v, &es, stream);
         if (r != GPS_OK) return r;
     }
     if (strips)

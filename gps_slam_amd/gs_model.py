@@ -121,6 +121,34 @@ class RawGaussianParams:
     def isDefined(self):
         return self.N > 0
 
+    # ---------------------------------------------------------------- per-frame exposure table [F,3,4] (raw_gs_param.cpp:61-65)
+    def exposureRows(self):
+        return 0 if self.exposure is None else self.exposure.shape[0]
+
+    def _reserve_exposure(self, rows, growing=False):
+        """a set table gets exactly its rows; a growing one (addGaussians) 4096 rows at first, then doubles"""
+        cap = 0 if getattr(self, "_exp_buf", None) is None else self._exp_buf.shape[0]
+        if rows <= cap:
+            return
+        nb = torch.empty((max(4096, rows, 2 * cap) if growing else rows, 3, 4), dtype=torch.float32, device=self.device)
+        F = self.exposureRows()
+        if F:
+            nb[:F] = self.exposure
+        self._exp_buf = nb
+        self.exposure = nb[:F]
+
+    def setExposure(self, table):
+        self.exposure = None
+        self._reserve_exposure(table.shape[0])
+        self.exposure = self._exp_buf[:table.shape[0]]
+        self.exposure.copy_(table)
+
+    def appendExposure(self, n):
+        F = self.exposureRows()
+        self._reserve_exposure(F + n, growing=True)
+        self._exp_buf[F:F + n] = torch.eye(3, 4, device=self.device)
+        self.exposure = self._exp_buf[:F + n]
+
     def getGaussianNum(self):
         return self.N
 
@@ -262,6 +290,10 @@ class RawGaussianModel:
         self._step_key = None
         self._B = None         # capacity-sized intermediates the step struct points at
         self._keep = None
+        # per-frame exposure (MODEL keys use_exposure / exposure_lr; host/raw_gs_model.cpp)
+        self.use_exposure = bool(cfg.get("use_exposure", False))
+        self.exposure_lr = cfg.get("exposure_lr", 0.003)
+        self._exp = None       # table optimiser: m / v / g at the table's capacity, slab, step count, rows with moments
 
     # ------------------------------------------------------------------ parameters
     def getGaussianNum(self):
@@ -344,6 +376,45 @@ class RawGaussianModel:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def exposure_row(self, cam):
+        """the camera's row of the exposure table, or -1 (exposure off, or cam.id outside [0, F))"""
+        return cam.id if self.use_exposure and 0 <= cam.id < self.opt_gs_params.exposureRows() else -1
+
+    def getExposure(self):
+        return self.opt_gs_params.exposure
+
+    def exposureGrad(self):
+        """the table's gradient of the last exposure step (zero outside the camera's row); None before the first one"""
+        if self._exp is None or self._exp["g"] is None:
+            return None
+        return self._exp["g"][:self.opt_gs_params.exposureRows()]
+
+    def exposureAdamState(self):
+        if self._exp is None or self._exp["m"] is None:
+            return []
+        F = self.opt_gs_params.exposureRows()
+        return [self._exp["m"][:F], self._exp["v"][:F]]
+
+    def _exposure_state(self, W, H):
+        p = self.opt_gs_params
+        cap = p._exp_buf.shape[0]
+        e = self._exp
+        if e["m"] is None or e["m"].shape[0] != cap:
+            keep = e["rows"] if e["m"] is not None else 0
+            for k in ("m", "v", "g"):
+                nb = torch.zeros((cap, 3, 4), device=self.device)
+                if k != "g" and keep:
+                    nb[:keep] = e[k][:keep]
+                e[k] = nb
+        n = int(lib.gps_exposure_slab_floats(W, H))
+        if e["slab"] is None or e["slab"].numel() < n:
+            e["slab"] = torch.empty(n, device=self.device)
+        F = p.exposureRows()
+        if e["step"] >= 1 and F > e["rows"]:   # rows appended since the last step start with zero moments
+            e["m"][e["rows"]:F] = 0
+            e["v"][e["rows"]:F] = 0
+        return e
+
     @staticmethod
     def clamp_ref_depth(ref_depth):
         """ref_depth_clamped = where(ref < 0.01, 1000, ref) (raw_gs_model.cpp:205-207)"""
@@ -358,9 +429,15 @@ class RawGaussianModel:
         self._bind_camera(st, cam, ref_depth_clamped, base_color, None)
         check(lib.gps_splat_render(C.byref(st), self._stream()), "gps_splat_render")
         B = self._B
-        check(lib.gps_compose_l1(cam.width, cam.height, B["render_colors"].data_ptr(), B["weight_sum"].data_ptr(),
-                                 base_color.data_ptr(), ref_depth.data_ptr(), None, B["rgb"].data_ptr(),
-                                 B["depth"].data_ptr(), None, None, None, self._stream()), "gps_compose_l1")
+        row = self.exposure_row(cam)
+        if row >= 0:
+            check(lib.gps_compose_exposure(cam.width, cam.height, B["render_colors"].data_ptr(), B["weight_sum"].data_ptr(),
+                                           base_color.data_ptr(), ref_depth.data_ptr(), self.getExposure()[row].data_ptr(),
+                                           B["rgb"].data_ptr(), B["depth"].data_ptr(), self._stream()), "gps_compose_exposure")
+        else:
+            check(lib.gps_compose_l1(cam.width, cam.height, B["render_colors"].data_ptr(), B["weight_sum"].data_ptr(),
+                                     base_color.data_ptr(), ref_depth.data_ptr(), None, B["rgb"].data_ptr(),
+                                     B["depth"].data_ptr(), None, None, None, self._stream()), "gps_compose_l1")
         N = self.getGaussianNum()
         return dict(rgb=B["rgb"], depth=B["depth"], alpha=B["weight_sum"][0], radiis=B["radii"][:N],
                     means2d=B["means2d"][:N])
@@ -378,6 +455,10 @@ class RawGaussianModel:
         # (an existing state is NOT zeroed: step 1 of gps_splat_train_step / gps_adam_step takes the moments as zero without reading
         # them and writes every live row -- include/gps_slam_hip.h, gps_adam_step)
         self._opt.update(lrs=lrs, step=0)
+        # exposureOpt (raw_gs_model.cpp:672): own state and step count
+        e = self._exp or dict(m=None, v=None, g=None, slab=None)
+        e.update(lr=float(f32(self.exposure_lr)), step=0, rows=0)
+        self._exp = e
 
     def grads(self):
         """parameter gradients of the last train_step, NAMES order ([:N] views)"""
@@ -408,8 +489,24 @@ class RawGaussianModel:
         else:
             armed = None
         o = self._opt
+        if o is None:
+            raise RuntimeError("initOptimizers() first")
+        row = self.exposure_row(cam)
+        st.exposure = st.exposure_grad = st.exposure_m = st.exposure_v = st.exposure_slab = None
+        st.exposure_rows, st.exposure_row, st.exposure_step, st.exposure_lr = 0, -1, 0, 0.0
+        if row >= 0:   # the camera has a row: the table is stepped in this call (its own step count)
+            e = self._exposure_state(cam.width, cam.height)
+            st.exposure, st.exposure_grad = self.opt_gs_params._exp_buf.data_ptr(), e["g"].data_ptr()
+            st.exposure_m, st.exposure_v, st.exposure_slab = e["m"].data_ptr(), e["v"].data_ptr(), e["slab"].data_ptr()
+            st.exposure_rows, st.exposure_row = self.opt_gs_params.exposureRows(), row
+            st.exposure_step, st.exposure_lr = e["step"] + 1, e["lr"]
         o["step"] += 1
-        check(lib.gps_splat_train_step(C.byref(st), o["step"], self._stream()), "gps_splat_train_step")  # raises on error: nothing armed
+        rc = lib.gps_splat_train_step(C.byref(st), o["step"], self._stream())
+        st.exposure = None   # (the struct is shared with the render path)
+        check(rc, "gps_splat_train_step")  # raises on error: nothing armed
+        if row >= 0:
+            self._exp["step"] += 1
+            self._exp["rows"] = self.opt_gs_params.exposureRows()
         self._prefetched = armed
 
     def loss_sum(self):
@@ -494,5 +591,12 @@ class SLAMGaussianModel(RawGaussianModel):
         # id order and gathers the gradient image per pixel -- with random ids every XCD's 4 MB L2 thrashes over the whole
         # 7 MB image (rocprofv3 FETCH_SIZE: 190 MB per launch); with pixel order its working set is a narrow band.
         perm = torch.randperm(n, generator=generator)[:num_select].sort().values.to(verts.device)  # CPU generator: n is host-known
+        was_empty = not self.opt_gs_params.isDefined()
         self.add_params(self.init_params(verts[perm].contiguous(), cols[perm], norms[perm]))
+        # exposure table (slam_gs_model.cpp:39-47): frame_num identity rows appended, or in place of the table of an empty model
+        if self.use_exposure and frame_num > 0:
+            if was_empty:
+                self.opt_gs_params.setExposure(torch.eye(3, 4, device=self.device).repeat(frame_num, 1, 1))
+            else:
+                self.opt_gs_params.appendExposure(frame_num)
         return num_select

@@ -103,6 +103,8 @@ PYBIND11_MODULE(_host, m) {
         .def("getFeaturesDc", &RawGaussianParams::getFeaturesDc)
         .def("getFeaturesRest", &RawGaussianParams::getFeaturesRest)
         .def("getOpacities", &RawGaussianParams::getOpacities)
+        .def("getExposure", &RawGaussianParams::getExposure)
+        .def("setExposure", &RawGaussianParams::setExposure)
         .def("add", [](RawGaussianParams& p, std::vector<torch::Tensor> t) { p.add(t); })
         .def("remove", &RawGaussianParams::remove)
         .def("savePly", &RawGaussianParams::savePly)
@@ -139,6 +141,11 @@ PYBIND11_MODULE(_host, m) {
         .def("optimizersZeroGrad", &SLAMGaussianModel::optimizersZeroGrad)
         .def("prunePoints", &SLAMGaussianModel::prunePoints)
         .def("grads", &SLAMGaussianModel::grads)
+        .def("getExposure", &SLAMGaussianModel::getExposure)
+        .def("exposureGrad", &SLAMGaussianModel::exposureGrad)
+        .def("exposureAdamState", &SLAMGaussianModel::exposureAdamState)
+        .def("exposureStep", &SLAMGaussianModel::exposureStep)
+        .def_readonly("use_exposure", &SLAMGaussianModel::use_exposure)
         .def("getGaussianNum", &SLAMGaussianModel::getGaussianNum)
         .def("getGaussianParms", &SLAMGaussianModel::getGaussianParms, py::return_value_policy::reference_internal)
         .def("getRealScales", &SLAMGaussianModel::getRealScales)

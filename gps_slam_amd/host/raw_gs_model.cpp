@@ -31,6 +31,8 @@ void RawGaussianModel::loadConfig(const Config& c) {
     fuse_sh_rest_adam = c.get("fuse_sh_rest_adam", fuse_sh_rest_adam ? 1.0 : 0.0) != 0.0;
     strip_backward = c.get("strip_backward", strip_backward ? 1.0 : 0.0) != 0.0;
     render_method = c.gets("render_method", render_method);
+    use_exposure = c.get("use_exposure", use_exposure ? 1.0 : 0.0) != 0.0;
+    exposure_lr = c.get("exposure_lr", exposure_lr);
     const int64_t cap = (int64_t)c.get("capacity", 1 << 19);
     opt_gs_params.reserve(cap, numShBases(maxSH), device);
 }
@@ -246,6 +248,34 @@ struct GesRenderFunction : public torch::autograd::Function<GesRenderFunction> {
     }
 };
 
+// grad-mode exposure transform (raw_gs_model.cpp:341-345: matmul(rgb, E[:, :3].t()) + E[:, 3].t()) on the composed image:
+// inputs rgb [H,W,3] and the table leaf [F,3,4]; backward -> d rgb and the full-table gradient (zero outside `row`), the latter
+// as a fixed-order reduction of per-workgroup partials (no atomics)
+struct ExposureFunction : public torch::autograd::Function<ExposureFunction> {
+    static torch::Tensor forward(AutogradContext* ctx, torch::Tensor rgb, torch::Tensor table, int64_t row, torch::Tensor slab) {
+        auto x = rgb.contiguous();
+        auto out = torch::empty_like(x);
+        check(gps_exposure_fwd((int)(x.numel() / 3), fptr(x), fptr(table) + 12 * row, fptr(out), current_stream()),
+              "gps_exposure_fwd");
+        ctx->saved_data["row"] = row;
+        ctx->save_for_backward({x, table, slab});
+        return out;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list g) {
+        auto saved = ctx->get_saved_variables();
+        const torch::Tensor &x = saved[0], &table = saved[1], &slab = saved[2];
+        const int64_t row = ctx->saved_data["row"].toInt();
+        auto v_out = g[0].contiguous();
+        auto v_rgb = torch::empty_like(x);
+        auto v_table = torch::empty({table.size(0), 3, 4}, table.options());
+        check(gps_exposure_bwd((int)(x.numel() / 3), fptr(x), fptr(table) + 12 * row, fptr(v_out), fptr(v_rgb), fptr(slab),
+                               current_stream()), "gps_exposure_bwd");
+        check(gps_exposure_reduce(fptr(slab), GPS_EXPOSURE_BWD_PARTIALS, (int)table.size(0), (int)row, fptr(v_table),
+                                  current_stream()), "gps_exposure_reduce");
+        return {v_rgb, v_table, torch::Tensor(), torch::Tensor()};
+    }
+};
+
 }  // namespace
 
 TensorDict RawGaussianModel::forward(const Camera& cam, const torch::Tensor& ref_depth, const torch::Tensor& base_color) {
@@ -309,14 +339,26 @@ TensorDict RawGaussianModel::gesForward(const Camera& cam, const torch::Tensor& 
                                             (int64_t)reinterpret_cast<intptr_t>(this),
                                             (int64_t)reinterpret_cast<intptr_t>(&cam), ref_depth, ref_clamped, base_color);
         res["rgb"] = out[0]; res["depth"] = out[1]; res["alpha"] = out[2];
+        const int row = exposureRow(cam);
+        if (row >= 0) {
+            TORCH_CHECK(exp_leaf_.defined() && exp_leaf_.size(0) == opt_gs_params.exposureRows(),
+                        "gesForward: the exposure table changed since initOptimizers() / the last structure edit");
+            res["rgb"] = ExposureFunction::apply(out[0], exp_leaf_, (int64_t)row, exposureSlab(cam.width, cam.height));
+        }
     } else {
         gps_splat_step& st = stepStruct(cam.width, cam.height);
         bindCamera(st, cam, ref_clamped, base_color, torch::Tensor());
         check(gps_splat_render(&st, current_stream()), "gps_splat_render");
         nextLaunchId();
-        check(gps_compose_l1(cam.width, cam.height, fptr(B_.render_colors), fptr(B_.weight_sum), fptr(base_color),
-                             fptr(ref_depth), nullptr, fptr(B_.rgb), fptr(B_.depth), nullptr, nullptr, nullptr,
-                             current_stream()), "gps_compose_l1");
+        const int row = exposureRow(cam);
+        if (row >= 0)
+            check(gps_compose_exposure(cam.width, cam.height, fptr(B_.render_colors), fptr(B_.weight_sum), fptr(base_color),
+                                       fptr(ref_depth), fptr(opt_gs_params.getExposure()) + 12 * row, fptr(B_.rgb), fptr(B_.depth),
+                                       current_stream()), "gps_compose_exposure");
+        else
+            check(gps_compose_l1(cam.width, cam.height, fptr(B_.render_colors), fptr(B_.weight_sum), fptr(base_color),
+                                 fptr(ref_depth), nullptr, fptr(B_.rgb), fptr(B_.depth), nullptr, nullptr, nullptr,
+                                 current_stream()), "gps_compose_l1");
         res["rgb"] = B_.rgb; res["depth"] = B_.depth; res["alpha"] = B_.weight_sum.index({0});
     }
     res["radiis"] = B_.radii.slice(0, 0, N);
@@ -366,6 +408,43 @@ void RawGaussianModel::setParamsRequireGrad() {
         v.set_requires_grad(true);
         leaf_.push_back(v);
     }
+    exp_leaf_ = torch::Tensor();
+    if (use_exposure && opt_gs_params.exposureRows() > 0) {
+        exp_leaf_ = opt_gs_params.getExposure().detach();
+        exp_leaf_.set_requires_grad(true);
+    }
+}
+
+void RawGaussianModel::exposureState() {
+    const int64_t cap = opt_gs_params.exposureCapacity();
+    if (cap == 0 || (exp_m_.defined() && exp_m_.size(0) == cap)) return;
+    const int64_t keep = exp_m_.defined() ? std::min<int64_t>(exp_state_rows_, exp_m_.size(0)) : 0;
+    auto grow = [&](torch::Tensor& t, bool copy) {
+        auto nb = torch::zeros({cap, 3, 4}, f32(device));
+        if (copy && keep > 0) nb.slice(0, 0, keep).copy_(t.slice(0, 0, keep));
+        t = nb;
+    };
+    grow(exp_m_, true); grow(exp_v_, true); grow(exp_g_, false);
+}
+
+torch::Tensor RawGaussianModel::exposureSlab(int W, int H) {
+    const int64_t n = gps_exposure_slab_floats(W, H);
+    if (!exp_slab_.defined() || exp_slab_.numel() < n) exp_slab_ = torch::empty({n}, f32(device));
+    return exp_slab_;
+}
+
+torch::Tensor RawGaussianModel::exposureGrad() {
+    const int64_t F = opt_gs_params.exposureRows();
+    return exp_g_.defined() ? exp_g_.slice(0, 0, std::min<int64_t>(F, exp_g_.size(0))) : torch::Tensor();
+}
+
+std::vector<torch::Tensor> RawGaussianModel::exposureAdamState() {
+    std::vector<torch::Tensor> out;
+    if (!have_opt_ || !exp_m_.defined()) return out;
+    const int64_t F = std::min<int64_t>(opt_gs_params.exposureRows(), exp_m_.size(0));
+    out.push_back(exp_m_.slice(0, 0, F));
+    out.push_back(exp_v_.slice(0, 0, F));
+    return out;
 }
 
 void RawGaussianModel::initOptimizers(int max_iterations, float scene_scale) {
@@ -391,6 +470,11 @@ void RawGaussianModel::initOptimizers(int max_iterations, float scene_scale) {
     lrs_[0] = (double)((float)means_lr * scene_scale); lrs_[1] = (double)(float)scales_lr; lrs_[2] = (double)(float)quats_lr;
     lrs_[3] = (double)(float)featuresDc_lr; lrs_[4] = (double)(float)featuresRest_lr; lrs_[5] = (double)(float)opacities_lr;
     adam_step_ = 0;
+    // exposureOpt (raw_gs_model.cpp:672): its own state and step count, lr widened from the float member like the others
+    exp_lr_ = (double)(float)exposure_lr;
+    exp_step_ = 0;
+    exp_state_rows_ = 0;
+    if (use_exposure) exposureState();
     have_opt_ = true;
     setParamsRequireGrad();
 }
@@ -398,14 +482,22 @@ void RawGaussianModel::initOptimizers(int max_iterations, float scene_scale) {
 void RawGaussianModel::reserveWorkspace(int width, int height) {
     stepStruct(width, height);
     const bool had = have_opt_;
-    const int step = adam_step_;
+    const int step = adam_step_, exp_step = exp_step_;
+    const int64_t exp_rows = exp_state_rows_;
     initOptimizers(-1, 1.0f);  // allocates m / v / g at capacity
     have_opt_ = had;           // ... but leaves the optimiser logically un-initialised if it was
     adam_step_ = step;
+    exp_step_ = exp_step; exp_state_rows_ = exp_rows;
 }
 
 void RawGaussianModel::optimizersZeroGrad() {
     for (auto& t : leaf_) t.mutable_grad() = torch::Tensor();
+    if (exp_leaf_.defined()) exp_leaf_.mutable_grad() = torch::Tensor();
+}
+
+// The moments of table rows appended since the optimiser last stepped are zero (a fresh optimiser: nothing to do)
+static void zero_new_exposure_rows(const torch::Tensor& m, const torch::Tensor& v, int64_t from, int64_t to, int next_step) {
+    if (next_step > 1 && to > from) { m.slice(0, from, to).zero_(); v.slice(0, from, to).zero_(); }
 }
 
 void RawGaussianModel::optimizersStep() {
@@ -426,6 +518,22 @@ void RawGaussianModel::optimizersStep() {
     }
     adam_step_ += 1;
     check(gps_adam_step(seg, 6, kAdamBeta1, kAdamBeta2, kAdamEps, adam_step_, current_stream()), "gps_adam_step");
+    // exposureOpt->step(): only when the table has a gradient (the iteration's camera has a row); the whole table is stepped
+    if (exp_leaf_.defined() && exp_leaf_.grad().defined()) {
+        exposureState();
+        const int64_t F = exp_leaf_.size(0);
+        TORCH_CHECK(F == opt_gs_params.exposureRows(), "optimizersStep: the exposure table changed under its gradient");
+        auto g = exp_leaf_.grad().contiguous();
+        exp_g_.slice(0, 0, F).copy_(g);
+        zero_new_exposure_rows(exp_m_, exp_v_, exp_state_rows_, F, exp_step_ + 1);
+        gps_adam_segment es;
+        es.param = fptr(opt_gs_params.exposureBuffer()); es.grad = fptr(g);
+        es.exp_avg = fptr(exp_m_); es.exp_avg_sq = fptr(exp_v_);
+        es.numel = F * 12; es.lr = exp_lr_;
+        exp_step_ += 1;
+        check(gps_adam_step(&es, 1, kAdamBeta1, kAdamBeta2, kAdamEps, exp_step_, current_stream()), "gps_adam_step(exposure)");
+        exp_state_rows_ = F;
+    }
 }
 
 void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_depth, const torch::Tensor& base_color,
@@ -444,8 +552,22 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
     const bool ahead = next_cam && next_cam->on_device() && next_cam->width == cam.width && next_cam->height == cam.height &&
                        gps_splat_can_prefetch(&st);
     if (ahead) { st.next_viewmat = next_cam->viewmat(); st.next_Kmat = next_cam->Kmat(); st.next_cam_pos = next_cam->cam_pos(); }
+    const int row = exposureRow(cam);
+    st.exposure = nullptr; st.exposure_grad = st.exposure_m = st.exposure_v = st.exposure_slab = nullptr;
+    st.exposure_rows = 0; st.exposure_row = -1; st.exposure_step = 0; st.exposure_lr = 0;
+    if (row >= 0) {   // the camera has a row: the table is stepped in this call (its own count)
+        exposureState();
+        const int64_t F = opt_gs_params.exposureRows();
+        zero_new_exposure_rows(exp_m_, exp_v_, exp_state_rows_, F, exp_step_ + 1);
+        st.exposure = fptr(opt_gs_params.exposureBuffer()); st.exposure_grad = fptr(exp_g_);
+        st.exposure_m = fptr(exp_m_); st.exposure_v = fptr(exp_v_); st.exposure_slab = fptr(exposureSlab(cam.width, cam.height));
+        st.exposure_rows = (int32_t)F; st.exposure_row = row; st.exposure_step = exp_step_ + 1; st.exposure_lr = exp_lr_;
+    }
     adam_step_ += 1;
-    check(gps_splat_train_step(&st, adam_step_, current_stream()), "gps_splat_train_step");   // throws on error: nothing armed then
+    const int rc = gps_splat_train_step(&st, adam_step_, current_stream());
+    st.exposure = nullptr;   // (the struct is shared with the render paths)
+    check(rc, "gps_splat_train_step");   // throws on error: nothing armed then
+    if (row >= 0) { exp_step_ += 1; exp_state_rows_ = opt_gs_params.exposureRows(); }
     if (ahead) prefetched_ = PrefetchKey{next_cam->pack_serial(), (int64_t)st.N, cam.width, cam.height, opt_gs_params.version()};
     nextLaunchId();
 }
@@ -490,7 +612,6 @@ void RawGaussianModel::applyPendingPrunes() {
 // ------------------------------------------------------------------------------------------------ addGaussians
 int SLAMGaussianModel::addGaussians(const Camera& cam, const TensorDict& frame_maps, const torch::Tensor& sample_mask,
                                     float new_gs_sample_ratio, int frame_num, c10::optional<at::Generator> gen) {
-    (void)frame_num;
     const int64_t H = cam.image.size(0), W = cam.image.size(1), P = H * W;
     const auto dev = cam.image.device();
     // The reference materialises three masked_select results (each a nonzero + gather with its own host round trip) and then
@@ -552,7 +673,14 @@ int SLAMGaussianModel::addGaussians(const Camera& cam, const TensorDict& frame_m
                                   gpsh::fptr(normal), gpsh::fptr(verts), gpsh::fptr(cols), gpsh::fptr(norms),
                                   (gps_stream)stream.stream()), "gps_gather_pixels");
     if (!opt_gs_params.buffer(0).defined()) opt_gs_params.reserve(1 << 19, numShBases(maxSH), verts.device());
+    const bool was_empty = !opt_gs_params.isDefined();
     opt_gs_params.appendInit(verts, cols, norms, maxSH, defaultOpacities, maxInitScale, minInitScale);
+    // the exposure table (slam_gs_model.cpp:39-47: init(..., frame_num) + add): frame_num identity rows behind the existing ones,
+    // or in place of them when the model was empty
+    if (use_exposure && frame_num > 0) {
+        if (was_empty) opt_gs_params.setExposure(torch::eye(3, 4, gpsh::f32(dev)).unsqueeze(0).repeat({frame_num, 1, 1}));
+        else opt_gs_params.appendExposure(frame_num);
+    }
     if (!leaf_.empty()) setParamsRequireGrad();
     return (int)num_select;
 }

@@ -81,6 +81,18 @@ public:
         return out;
     }
 
+    // Per-frame exposure (use_exposure; raw_gs_model.cpp:331-346, :672): the table [F,3,4], its gradient of the last iteration
+    // (zero outside the camera's row) and its Adam moments {exp_avg, exp_avg_sq} as [:F] views (empty before initOptimizers;
+    // rows the optimiser has not stepped yet are undefined, as in adamState()).  The table has its own step count.
+    torch::Tensor getExposure() { return opt_gs_params.getExposure(); }
+    torch::Tensor exposureGrad();
+    std::vector<torch::Tensor> exposureAdamState();
+    int exposureStep() const { return exp_step_; }
+    // the camera's row of the table, or -1: exposure off, or cam.id outside [0, F)
+    int exposureRow(const Camera& cam) const {
+        return use_exposure && cam.id >= 0 && cam.id < opt_gs_params.exposureRows() ? cam.id : -1;
+    }
+
     static torch::Tensor clampRefDepth(const torch::Tensor& ref_depth);  // raw_gs_model.cpp:205-207
 
     RawGaussianParams opt_gs_params;
@@ -101,6 +113,8 @@ public:
     // trainStep's binning + backward rasterizer: superblock counting sort + column strips (gps_splat_step::v_rows .. set), or
     // the sorted-key binning + 32-pixel-group kernel of the operator-level entry points
     bool strip_backward = true;
+    bool use_exposure = false;   // MODEL keys use_exposure / exposure_lr (configs/release/*/*.yaml:101-102)
+    double exposure_lr = 0.003;
     std::string render_method = "ges";
     bool abs_grad = false;       // raw_gs_model.h:293
     torch::Tensor backgrounds;   // raw_gs_model.h:295 ([1,4] device tensor; undefined = none)
@@ -145,6 +159,14 @@ protected:
     int64_t adam_cap_ = -1;
     int adam_step_ = 0;
     bool have_opt_ = false;
+    // exposure table: Adam state / gradient sized like the table's capacity buffer, the slab of per-workgroup d E partials, the
+    // step count, and the autograd leaf of the grad-mode forward
+    torch::Tensor exp_m_, exp_v_, exp_g_, exp_slab_, exp_leaf_;
+    int exp_step_ = 0;
+    int64_t exp_state_rows_ = 0;   // rows whose moments the optimiser has written (rows appended since start from zero)
+    double exp_lr_ = 0;
+    void exposureState();          // (re)size the table's optimiser buffers to the table's capacity
+    torch::Tensor exposureSlab(int W, int H);
     std::vector<torch::Tensor> leaf_;  // parameter leaves handed to autograd by the last grad-mode forward
     std::vector<torch::Tensor> keep_;  // inputs of the last launch, kept alive until the next one
     struct PendingPrune { torch::Tensor keep; int64_t n_before; };

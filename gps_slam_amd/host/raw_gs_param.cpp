@@ -140,7 +140,35 @@ void RawGaussianParams::init(const torch::Tensor& xyz, const torch::Tensor& rgb,
     reserve(std::max<int64_t>(cap_, std::max<int64_t>(1 << 19, 2 * xyz.size(0))), numShBases(max_sh_degree), xyz.device());
     N_ = 0;
     add(t);
-    exposure = torch::eye(3, 4, xyz.options()).unsqueeze(0).repeat({exposure_num, 1, 1});  // raw_gs_param.cpp:70-73
+    setExposure(torch::eye(3, 4, xyz.options()).unsqueeze(0).repeat({exposure_num, 1, 1}));  // raw_gs_param.cpp:70-73
+}
+
+void RawGaussianParams::reserveExposure(int64_t rows, const torch::Device& device, bool growing) {
+    if (exp_buf_.defined() && rows <= exp_buf_.size(0)) return;
+    const int64_t F = exposureRows();
+    // a table that is only set (init, loadTensor: what use_exposure off ever does) gets exactly its rows; one that grows, room ahead
+    const int64_t cap = growing ? std::max<int64_t>(4096, std::max<int64_t>(rows, 2 * exposureCapacity())) : rows;
+    auto nb = torch::empty({cap, 3, 4}, f32(device));
+    if (F > 0) nb.slice(0, 0, F).copy_(exposure);
+    exp_buf_ = nb;
+    exposure = exp_buf_.slice(0, 0, F);
+}
+
+void RawGaussianParams::setExposure(const torch::Tensor& table) {
+    TORCH_CHECK(table.dim() == 3 && table.size(1) == 3 && table.size(2) == 4, "exposure table: [F,3,4]");
+    const int64_t F = table.size(0);
+    exposure = torch::Tensor();   // (nothing to keep)
+    reserveExposure(F, table.is_cuda() ? table.device() : device_);
+    exposure = exp_buf_.slice(0, 0, F);
+    exposure.copy_(table);
+}
+
+void RawGaussianParams::appendExposure(int64_t n) {
+    if (n <= 0) return;
+    const int64_t F = exposureRows();
+    reserveExposure(F + n, exp_buf_.defined() ? exp_buf_.device() : device_, true);
+    exp_buf_.slice(0, F, F + n).copy_(torch::eye(3, 4, exp_buf_.options()).unsqueeze(0).expand({n, 3, 4}));
+    exposure = exp_buf_.slice(0, 0, F + n);
 }
 
 void RawGaussianParams::add(const std::vector<torch::Tensor>& t) {
@@ -154,9 +182,21 @@ void RawGaussianParams::add(const std::vector<torch::Tensor>& t) {
 }
 
 void RawGaussianParams::add(const RawGaussianParams& other) {
+    // the exposure table as raw_gs_param.cpp:123-145 treats it: an empty model takes the other's, otherwise its rows are appended
+    const bool was_empty = !isDefined();
     std::vector<torch::Tensor> t;
     for (int k = 0; k < NUM; k++) t.push_back(other.view(k));
     add(t);
+    if (other.exposureRows() > 0) {
+        if (was_empty) {
+            setExposure(other.exposure);
+        } else {
+            const int64_t F = exposureRows(), n = other.exposureRows();
+            reserveExposure(F + n, other.exposure.device(), true);
+            exp_buf_.slice(0, F, F + n).copy_(other.exposure);
+            exposure = exp_buf_.slice(0, 0, F + n);
+        }
+    }
 }
 
 void RawGaussianParams::remove(const torch::Tensor& mask) { removeKeep(~mask); }
@@ -222,7 +262,7 @@ void RawGaussianParams::saveTensor(const std::string& filename) const {
     torch::serialize::OutputArchive archive;
     static const char* names[NUM] = {"means", "scales", "quats", "featuresDc", "featuresRest", "opacities"};
     for (int k = 0; k < NUM; k++) archive.write(names[k], view(k).contiguous());
-    archive.write("exposure", exposure.defined() ? exposure : torch::eye(3, 4, f32(device_)).unsqueeze(0));
+    archive.write("exposure", exposure.defined() ? exposure.clone() : torch::eye(3, 4, f32(device_)).unsqueeze(0));   // (own storage: not the capacity buffer)
     archive.save_to(filename);
 }
 
@@ -232,8 +272,9 @@ void RawGaussianParams::loadTensor(const std::string& filename) {
     static const char* names[NUM] = {"means", "scales", "quats", "featuresDc", "featuresRest", "opacities"};
     std::vector<torch::Tensor> t(NUM);
     for (int k = 0; k < NUM; k++) { archive.read(names[k], t[k]); t[k] = t[k].to(device_); }
-    archive.read("exposure", exposure);
-    exposure = exposure.to(device_);
+    torch::Tensor table;
+    archive.read("exposure", table);
+    setExposure(table.to(device_));
     N_ = 0;
     add(t);
 }

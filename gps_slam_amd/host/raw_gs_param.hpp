@@ -85,7 +85,13 @@ public:
     torch::Tensor getFeaturesDc() const { return view(3); }
     torch::Tensor getFeaturesRest() const { return view(4); }
     torch::Tensor getOpacities() const { return view(5); }
+    // the per-frame exposure table [F,3,4] (raw_gs_param.cpp:61-65): an [:F] view of a capacity-sized device buffer
     torch::Tensor getExposure() const { return exposure; }
+    int64_t exposureRows() const { return exposure.defined() ? exposure.size(0) : 0; }
+    int64_t exposureCapacity() const { return exp_buf_.defined() ? exp_buf_.size(0) : 0; }
+    torch::Tensor exposureBuffer() const { return exp_buf_; }
+    void setExposure(const torch::Tensor& table);   // the table := a copy of `table` [F,3,4]
+    void appendExposure(int64_t n);                 // n identity rows behind the existing ones
     torch::Tensor getRealMeans() const { return view(0); }
     torch::Tensor getRealScales() const { return torch::exp(view(1)); }
     torch::Tensor getRealOpacities() const { return torch::sigmoid(view(5)); }
@@ -99,7 +105,12 @@ public:
 protected:
     torch::Tensor view(int k) const { return buf_[k].defined() ? buf_[k].slice(0, 0, N_) : torch::Tensor(); }
     torch::Tensor buf_[NUM], alt_[NUM];
-    torch::Tensor exposure;
+    torch::Tensor exposure;   // [:F] view of exp_buf_
+    // Set tables (init, loadTensor, setExposure) get exactly their rows.  A growing one (addGaussians with use_exposure: the map
+    // worker, which is also the only thread that trains with the table) gets 4096 rows (196 KB) at its first growth and is then
+    // doubled with a stream-ordered copy on that thread, so a sequence of up to ~4000 frames moves it once.
+    torch::Tensor exp_buf_;
+    void reserveExposure(int64_t rows, const torch::Device& device, bool growing = false);
     mutable torch::Tensor keep_idx_;
     torch::Tensor keep_ids32_, host_count_;
     int64_t N_ = 0, cap_ = 0;

@@ -64,7 +64,8 @@ GPS_API const char *gps_build_flags(void);
 #define GPS_TIMED_SB_SCATTER 5
 #define GPS_TIMED_INTEGRATE 6
 #define GPS_TIMED_RAYCAST 7
-#define GPS_TIMED_KINDS 8
+#define GPS_TIMED_EXPOSURE 8 /* the per-frame exposure kernels (gps_exposure_*, the train step's table reduce + Adam launch) */
+#define GPS_TIMED_KINDS 9
 GPS_API int gps_launch_timing_start(int capacity);
 GPS_API int gps_launch_timing_stop(void);
 GPS_API int gps_launch_timing_read(int kind, double *total_us, int64_t *launches, double *total_us_flagged,
@@ -299,6 +300,25 @@ GPS_API int gps_compose_l1(int width, int height, const float *render_colors, co
                    const float *base_color, const float *ref_depth_raw, const float *gt_rgb, float *rgb,
                    float *depth, float *loss, float *v_render_colors, float *v_render_alphas, gps_stream stream);
 
+/* Per-frame exposure, operator level (use_exposure; raw_gs_model.cpp:331-346).  `row` is ONE camera's [3,4] row-major entry E of
+ * the exposure table (device):  out[p,i] = sum_j rgb[p,j] E[i][j] + E[i][3].
+ * gps_compose_exposure: gps_compose_l1's render-only call (gt_rgb NULL) with E applied to the composed colour (depth untouched):
+ * the NoGradGuard forward.  gps_exposure_fwd: out = E(rgb) for n_pixels rows of rgb[n,3].  gps_exposure_bwd: v_rgb[p,j] =
+ * sum_i v_out[p,i] E[i][j], and the 12 partials of d/dE (sum_p v_out[p,i] rgb[p,j], sum_p v_out[p,i]) of each of its
+ * GPS_EXPOSURE_BWD_PARTIALS workgroups into slab[GPS_EXPOSURE_BWD_PARTIALS, 12] (no atomics).  gps_exposure_reduce: the
+ * fixed-order sum of n_partials such rows of 12 -> grad[rows,3,4] (row `row` = the sum, every other row 0): bit-identical run to
+ * run.  gps_exposure_slab_floats: the slab size (floats) that serves both the train step (one row per 16 x 16 tile) and
+ * gps_exposure_bwd at width x height. */
+#define GPS_EXPOSURE_BWD_PARTIALS 1024
+GPS_API int64_t gps_exposure_slab_floats(int width, int height);
+GPS_API int gps_compose_exposure(int width, int height, const float *render_colors, const float *weight_sum,
+                                 const float *base_color, const float *ref_depth_raw, const float *row, float *rgb, float *depth,
+                                 gps_stream stream);
+GPS_API int gps_exposure_fwd(int n_pixels, const float *rgb, const float *row, float *out, gps_stream stream);
+GPS_API int gps_exposure_bwd(int n_pixels, const float *rgb, const float *row, const float *v_out, float *v_rgb, float *slab,
+                             gps_stream stream);
+GPS_API int gps_exposure_reduce(const float *slab, int n_partials, int rows, int row, float *grad, gps_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* Splat: fused multi-tensor Adam                                      */
 /* ------------------------------------------------------------------ */
@@ -513,6 +533,18 @@ typedef struct {
      * buffers in between): its preprocessing launch is skipped.  Same arithmetic on the same values as the separate launch. */
     const float *next_viewmat, *next_Kmat, *next_cam_pos;
     int32_t preprocessed;
+    /* Per-frame exposure compensation (use_exposure; raw_gs_model.cpp:331-346).  All zero (the default) = off, and the step runs
+     * exactly as without these fields.  exposure: the [exposure_rows, 3, 4] row-major table E (rgb_out[i] = sum_j rgb[j] E[r][i][j]
+     * + E[r][i][3] on the composed image); exposure_row = r, the camera's row (cam.id; -1 = none).  With 0 <= r < exposure_rows the
+     * train step applies E[r] in the forward rasterizer's compose + L1 epilogue, reduces d loss / d E[r] per tile into
+     * exposure_slab (gps_exposure_slab_floats(width, height) floats, no atomics) and runs ONE more small launch between the forward
+     * rasterizer and the backward (it needs only the slab; the backward does not read the table): the fixed-order slab sum,
+     * exposure_grad := the full-table gradient (zero outside row r) and an Adam step number exposure_step (1-based, counted apart
+     * from adam_step) of the whole table with exposure_lr and beta1 / beta2 / adam_eps above (exposure_m / exposure_v: its moments,
+     * [exposure_rows, 3, 4]).  Otherwise the table is neither read nor stepped.  Needs the record forward (records != NULL). */
+    float *exposure, *exposure_grad, *exposure_m, *exposure_v, *exposure_slab;
+    int32_t exposure_rows, exposure_row, exposure_step;
+    double exposure_lr;
 } gps_splat_step;
 
 /* != 0: gps_splat_train_step(a) can run the next iteration's preprocessing in its tail (strip backward + superblock binning in
