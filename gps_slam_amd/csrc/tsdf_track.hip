@@ -21,6 +21,10 @@
 //                             the one a RETIRED launch gives before the host reuses the argument line, once per frame)
 //   track_eval_kernel<ITER>   the same body as a plain launch with kernel arguments (host_mailbox == NULL, or the fall-back)
 //
+// The host half: LmLoop (the LM bookkeeping: request() / apply()), Handover (one frame's evaluation hand-over in every transport:
+// sequence numbers, argument lines, retirement, the bounded waits, the drain-and-redo fall-back) and track_camera_impl (prepare
+// launch, then the LM loop over Handover::evaluate / answer).
+//
 // What was tried in round 2 and measured slower (kept out of the tree): (1) the whole LM loop in ONE persistent launch with a
 // grid-wide rendezvous per iteration -- correct, but all its workgroups must be resident at once, and next to the map stream's
 // rasterizer kernels the big spinning workgroups starved behind a steady supply of small ones (800 -> 120 frames/s with the
@@ -206,7 +210,7 @@ constexpr int EV_MAX_WGS = GPS_TRACK_EV_MAX_WGS;           // rows of the partia
 constexpr int EV_ROW_GROUPS = EV_THREADS / 32;
 // Poses one pre-launched evaluation can take: the LM loop's next pose + the poses the loop would evaluate AFTER it if it is
 // rejected (they depend on the last good state only, so the host knows them before the evaluation returns -- see
-// track_camera_impl).  Each pose is evaluated by its own group of EV_MAX_WGS workgroups with its own argument line, row table
+// LmLoop::rejection_chain).  Each pose is evaluated by its own group of EV_MAX_WGS workgroups with its own argument line, row table
 // and result block.
 #ifndef GPS_TRACK_EV_GROUPS
 #define GPS_TRACK_EV_GROUPS 4
@@ -834,6 +838,20 @@ struct LmLoop {
         memcpy(r.pose, approxInvPose, 64);
         return r;
     }
+    // What the loop evaluates after the current request should that be rejected, and after that one, ... (at most n): the
+    // poses that ride along with the evaluation.  (The first evaluation of a level is only rejected when it has no valid pixel
+    // at all: nothing rides along with it.)
+    int rejection_chain(int n, LmRequest* out) const {
+        if (iter == 0) return 0;
+        LmLoop sim = *this;
+        int k = 0;
+        for (; k < n; k++) {
+            sim.apply(nullptr);
+            if (!sim.active) break;
+            out[k] = sim.request();
+        }
+        return k;
+    }
     // host = the 30 payload words of an evaluation's result (eval_body), or nullptr = the evaluation is taken as rejected.
     // Returns whether the evaluation was rejected.
     bool apply(const float* host) {
@@ -930,6 +948,305 @@ size_t carve(Scratch* w, char* base, int W, int H) {
     p = take((size_t)W * H * 2 * sizeof(float4)); if (w) w->pn = (float4*)p;
     return off;
 }
+
+// An evaluation's arguments for one level and pose: what track_eval_poll_kernel assembles from the frame's constants and its line
+GhArgs gh_args(const PollArgs& pl, int level, const float* pose) {
+    const LevelTab& lt = pl.tab[level];
+    GhArgs a;
+    a.depth = lt.depth; a.vw = lt.vw; a.vh = lt.vh;
+    a.view_intr = make_float4(lt.ix, lt.iy, lt.iz, lt.iw);
+    a.pn = pl.pn; a.sw = pl.sw; a.sh = pl.sh; a.scene_intr = pl.scene_intr;
+    a.approxInvPose = load_mat(pose); a.scenePose = pl.scenePose;
+    a.space_thresh = lt.space_thresh; a.tukey_cutoff = pl.tukey_cutoff; a.vf_min = pl.vf_min; a.vf_max = pl.vf_max;
+    a.use_weights = pl.use_weights; a.frames_to_skip = pl.frames_to_skip; a.frames_to_weight = pl.frames_to_weight;
+    return a;
+}
+
+// Polls done(spin) at most `budget` times -> whether it came true.  A result normally lands within ~20 us (a few thousand polls);
+// a host still spinning far beyond that is oversubscribed or the GPU is busy elsewhere: stop burning the core between polls.
+template <class Done>
+bool spin_until(long budget, Done done) {
+    for (long spin = 0; spin < budget; spin++) {
+        if (done(spin)) return true;
+        if ((spin & 0xFFFF) == 0xFFFF) sched_yield();
+    }
+    return false;
+}
+
+// One frame's evaluation hand-over, every transport; which one is decided once, from the state: plain launches read back by
+// memcpy (host_mailbox == NULL), or pre-launched evaluations (mailbox) told by the pinned line or the BAR line, answered by the
+// device's summer or by rows this thread adds (host_rows).  evaluate() returns once group 0 has answered, answer(g) gives group
+// g's; a pre-launched evaluation that has not been given its arguments is retired on every way out (the destructor).
+struct Handover {
+    gps_track_state* ts; hipStream_t st; Scratch w; int parity;
+    PollArgs pl;   // the frame's constants + the transport (the posted launches' kernel arguments)
+    volatile float* mailbox;
+    volatile uint32_t *arg_line, *bar_line, *host_rows;   // the pinned line; != NULL: the BAR lines / the host-summed row tables
+    int n_groups;                     // groups of a launch: the loop's pose + the poses that ride along (BAR line only)
+    int pending = 0;                  // the pre-launched evaluation that has not been given its arguments yet (0: none)
+    float raw[EV_GROUPS][GH_SLOTS];   // per group two 64-byte chunks: 15 payload words + the sequence number each (eval_fused)
+    int n_rows[EV_GROUPS];            // rows of group g's table (the workgroups of its level)
+    int answers = 0;                  // raw[0 .. answers) hold results: the evaluation itself, then the poses that rode along
+    int ride_seq = 0;                 // host-summed rows: the launch whose riding-along groups may still be collected (0: none)
+    int rows_next[EV_GROUPS]; float rows_part[EV_GROUPS][EV_ROW_GROUPS][GH_SLOTS];   // host_rows: added so far (answered())
+    Handover(const TsdfState& s, const gps_track_config* c, gps_track_state* ts_, const Scratch& w_, hipStream_t st_, const PrepArgs& pa)
+        : ts(ts_), st(st_), w(w_), parity(pa.parity), pl() {
+        pl.pn = w.pn; pl.sw = s.width; pl.sh = s.height;
+        pl.scene_intr = make_float4(s.fx, s.fy, s.cx, s.cy);
+        pl.scenePose = load_mat(ts->pose_pc_M);
+        pl.tukey_cutoff = c->tukey_cutoff; pl.vf_min = s.view_frustum_min; pl.vf_max = s.view_frustum_max;
+        pl.use_weights = ts->frames_processed >= 100; pl.frames_to_skip = c->frames_to_skip; pl.frames_to_weight = c->frames_to_weight;
+        for (int l = 0; l < GPS_TRACK_MAX_LEVELS; l++) pl.tab[l] = pa.tab_vals[l];
+        mailbox = reinterpret_cast<volatile float*>(ts->host_mailbox);
+        arg_line = mailbox ? reinterpret_cast<volatile uint32_t*>(ts->host_mailbox) + 48 : nullptr;
+        bar_line = mailbox ? reinterpret_cast<volatile uint32_t*>(ts->dev_arg_line) : nullptr;
+        // mailbox layout (gps_track_state.mailbox_bytes): G answer blocks of 256 bytes -- and, when there is room for them, G row
+        // tables of EV_MAX_WGS x 128 bytes behind the blocks: the workgroups then store their rows THERE and this thread adds them
+        constexpr int BLOCK_BYTES = MAILBOX_GROUP_WORDS * 4, ROWS_BYTES = EV_MAX_WGS * GH_SLOTS * 4;
+        static_assert(BLOCK_BYTES == GPS_TRACK_MAILBOX_BLOCK_BYTES && ROWS_BYTES == GPS_TRACK_MAILBOX_ROWS_BYTES, "include/gps_slam_hip.h");
+        const int groups_with_rows = ts->mailbox_bytes / (BLOCK_BYTES + ROWS_BYTES);
+        // (host-summed rows reproduce the device summer's bits only with IEEE float adds on this thread: with flush-to-zero or
+        // denormals-are-zero set in MXCSR -- e.g. a host built with -ffast-math that set them process-wide -- the device summer is
+        // used; round-5 advisor finding.  The 64-byte row chunks leave the device as single store instructions and are tagged in
+        // their last word; tests/test_tsdf_gpu.py keeps the host-summed == device-summed equality test in the default set)
+        const bool host_sums = mailbox && groups_with_rows >= 1 && !host_flushes_denormals();
+        const int mailbox_groups = host_sums ? groups_with_rows : ts->mailbox_bytes >= 2 * BLOCK_BYTES ? ts->mailbox_bytes / BLOCK_BYTES : 1;
+        n_groups = (mailbox && bar_line) ? max(1, min(EV_GROUPS, mailbox_groups)) : 1;
+        host_rows = host_sums ? reinterpret_cast<volatile uint32_t*>(ts->host_mailbox) + (size_t)min(EV_GROUPS, mailbox_groups) * MAILBOX_GROUP_WORDS : nullptr;
+        pl.arg_line = const_cast<const uint32_t*>(arg_line); pl.dev_line = w.dev_line;
+        pl.bar_line = const_cast<const uint32_t*>(bar_line); pl.host_rows = host_rows;
+    }
+    ~Handover() { if (pending) retire(pending); }
+    // Per-state sequence numbers (>= 1).  When they wrap, the line of the last launch before the wrap -- a LARGER number than
+    // everything that follows -- is wiped first: a late workgroup must not mistake it for a later launch's line, see `superseded`
+    // in the kernel.
+    int next_seq() {
+        if (ts->mail_seq >= 0x3FFFFFFF) {
+            ts->mail_seq = 0;
+            if (mailbox) mailbox[32] = 0.0f;   // (the retirement word compares like the line: retired())
+            if (bar_line) {
+                for (int k = 0; k < 8 * EV_GROUPS; k++) reinterpret_cast<volatile uint64_t*>(bar_line)[k] = 0;
+                host_store_fence();
+            }
+        }
+        return (int)(++ts->mail_seq);
+    }
+    // One argument line: payload first, sequence number last (x86 stores are not reordered with each other; the compiler barrier
+    // keeps the order).  Group g's line sits 64 bytes behind group g - 1's in the BAR block; the pinned line has group 0 only.
+    void write_line(int grp, int seq, uint32_t cmd, int kind, int level, const float* pose) {
+        uint32_t wds[16] = {0};
+        wds[1] = cmd | ((uint32_t)kind << 8) | ((uint32_t)level << 16);
+        if (pose)
+            for (int col = 0; col < 4; col++)
+                for (int r = 0; r < 3; r++) memcpy(&wds[2 + col * 3 + r], &pose[col * 4 + r], 4);
+        wds[0] = (uint32_t)seq;
+        uint32_t x = 0;
+        for (int k = 0; k < 15; k++) x ^= wds[k];
+        wds[15] = x;
+        if (bar_line) {
+            // through the BAR: the mapping is write-combining, so the 64 bytes gather in one of the core's WC buffers and leave
+            // as one posted write when the sfence drains it (without the fence the line sits there until something evicts
+            // it: tools/probe/pingpong.hip reads 560 us per round trip instead of 1.8).  A torn line fails the xor word.
+            volatile uint64_t* dst = reinterpret_cast<volatile uint64_t*>(bar_line + 16 * grp);
+            for (int k = 0; k < 16; k += 2) dst[k >> 1] = (uint64_t)wds[k] | ((uint64_t)wds[k + 1] << 32);
+            return;
+        }
+        for (int k = 1; k < 16; k++) arg_line[k] = wds[k];
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        arg_line[0] = wds[0];
+    }
+    // group 0's line, then the fence that sends every line written since the last one on its way
+    void publish(int seq, uint32_t cmd, int kind, int level, const float* pose) {
+        write_line(0, seq, cmd, kind, level, pose);
+        if (bar_line) host_store_fence();
+    }
+    // launch `seq` -- or a later one, which cannot have started before `seq` had drained -- has taken itself out (ARG_SKIP or its
+    // own ARG_TIMEOUT) and said so in mailbox word 32
+    bool retired(int seq) const { return (int32_t)((uint32_t)float_bits(mailbox[32]) - (uint32_t)seq) >= 0; }
+    // Retire a pre-launched evaluation the loop did not need: ARG_SKIP, then wait until the launch has SEEN it (mailbox word
+    // 32 := its sequence number).  Usually that launch is already polling and answers within a PCIe round trip; when it is
+    // still queued behind other streams' kernels the wait is what keeps the next frame's first arguments from overwriting the
+    // line it has yet to read (measured without it: 1 overlap run in ~10 lost 50 ms -- one ARG_TIMEOUT -- in a single frame).
+    void retire(int seq) {
+        for (int g = 1; g < n_groups; g++) write_line(g, seq, ARG_SKIP, 0, 0, nullptr);
+        publish(seq, ARG_SKIP, 0, 0, nullptr);
+        spin_until(400000000L, [&](long) { return retired(seq); });   // (bounded; the launch gives up by itself after ARG_TIMEOUT)
+    }
+    int prelaunch() {
+        pending = next_seq();
+        track_eval_poll_kernel<<<n_groups * EV_MAX_WGS, EV_THREADS, 0, st>>>(pl, w.partial, w.sync, w.result, mailbox, pending, parity);
+        return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+    }
+    // One evaluation as a plain launch with kernel arguments, waited for: its summer answers into mailbox block 0 (mb), or the
+    // sums are read back by memcpy (mb == NULL; the reference's GPU tracker reads its 32 accumulators back every iteration as well)
+    int eval_plain(const LmRequest& req, volatile float* mb) {
+        const int seq = next_seq();
+        const GhArgs a = gh_args(pl, req.level, req.pose);
+        const int n_wgs = pl.tab[req.level].n_wgs;
+        if (req.kind == TRK_ROTATION) track_eval_kernel<TRK_ROTATION><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, mb, seq, parity);
+        else if (req.kind == TRK_TRANSLATION) track_eval_kernel<TRK_TRANSLATION><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, mb, seq, parity);
+        else track_eval_kernel<TRK_BOTH><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, mb, seq, parity);
+        GPS_LAUNCH_CHECK();
+        if (!mb && hipMemcpyAsync(raw[0], w.result, sizeof(raw[0]), hipMemcpyDeviceToHost, st) != hipSuccess) GPS_FAIL_LAUNCH();
+        if (hipStreamSynchronize(st) != hipSuccess) GPS_FAIL_LAUNCH();
+        if (mb)
+            for (int k = 0; k < GH_SLOTS; k++) raw[0][k] = mb[k];
+        if (float_bits(raw[0][15]) != seq || float_bits(raw[0][31]) != seq) GPS_FAIL_LAUNCH();  // the summer gave up
+        return GPS_OK;
+    }
+    // The answer of group g to launch `seq`: the summer's block, or -- host_rows -- the rows of its table added in the summer's order
+    // (thread (r, k) of the summer adds word k of rows r, r + 8, ... in increasing order, then the eight partial sums in order:
+    // eval_fused / sum_rows_and_answer; IEEE additions only, so the bits are the device's).  `rows_next` remembers the first row not
+    // yet seen: rows are stable once tagged (nothing rewrites them before the next launch's lines are published).
+    // Rows are added AS THEY ARRIVE (in row order: the scan below only ever moves forward), so that the last row to land costs one
+    // row's additions, not a pass over the table.
+    bool answered(int g, int seq) {
+        if (!host_rows) {
+            volatile float* const mb = mailbox + g * MAILBOX_GROUP_WORDS;
+            return float_bits(mb[15]) == seq && float_bits(mb[31]) == seq;
+        }
+        volatile uint32_t* const T = host_rows + (size_t)g * EV_MAX_WGS * GH_SLOTS;
+        int& r = rows_next[g];
+        while (r < n_rows[g] && (int)T[r * GH_SLOTS + 15] == seq && (int)T[r * GH_SLOTS + 31] == seq) {
+            float* dst = rows_part[g][r % EV_ROW_GROUPS];
+            for (int k = 0; k < GH_SLOTS; k++) {
+                if ((k & 15) == 15) continue;   // the row's tags
+                const uint32_t v = T[r * GH_SLOTS + k]; float f; memcpy(&f, &v, 4); dst[k] += f;
+            }
+            r++;
+        }
+        return r >= n_rows[g];
+    }
+    // group g's answer to launch seq, waited for (bounded) and collected into raw[g]
+    bool take(int g, int seq) {
+        if (!spin_until(200000000L, [&](long) { return answered(g, seq); })) return false;
+        collect(g);
+        answers = g + 1;
+        return true;
+    }
+    void collect(int g) {   // (after answered(g): host_rows has added every row)
+        if (!host_rows) {
+            volatile float* const mb = mailbox + g * MAILBOX_GROUP_WORDS;
+            for (int k = 0; k < GH_SLOTS; k++) raw[g][k] = mb[k];
+            return;
+        }
+        volatile uint32_t* const T = host_rows + (size_t)g * EV_MAX_WGS * GH_SLOTS;
+        for (int k = 0; k < GH_SLOTS; k++) {
+            float t = 0.0f;
+            for (int q = 0; q < EV_ROW_GROUPS; q++) t += rows_part[g][q][k];
+            raw[g][k] = t;
+        }
+        const uint32_t vcount = T[30];   // payload 29 of row 0: the frame's valid-pixel count (bits)
+        memcpy(&raw[g][30], &vcount, 4);
+    }
+    // The evaluation of `req`, with the poses `cand[0 .. nc)` riding along -> GPS_OK once raw[0] holds its answer
+    int evaluate(const LmRequest& req, const LmRequest* cand, int nc, int iter) {
+        answers = 1;
+        ride_seq = 0;
+        if (!mailbox) return eval_plain(req, nullptr);
+        n_rows[0] = pl.tab[req.level].n_wgs;
+        for (int g = 1; g <= nc; g++) n_rows[g] = pl.tab[cand[g - 1].level].n_wgs;
+        // this evaluation is the pre-launched kernel (or the frame's first launch): hand it its arguments, then put the NEXT
+        // evaluation on the stream before waiting -- its launch cost overlaps this evaluation
+        if (!pending && prelaunch() != GPS_OK) GPS_FAIL_LAUNCH();
+        const int seq = pending;
+        pending = 0;
+        for (int g = 0; g < n_groups; g++) {   // (sequence numbers are >= 1: nothing stale can match)
+            mailbox[g * MAILBOX_GROUP_WORDS + 15] = 0.0f; mailbox[g * MAILBOX_GROUP_WORDS + 31] = 0.0f;
+            rows_next[g] = 0;
+            memset(rows_part[g], 0, sizeof(rows_part[g]));
+        }
+        for (int g = 1; g < n_groups; g++) {
+            if (g <= nc) write_line(g, seq, ARG_RUN, cand[g - 1].kind, cand[g - 1].level, cand[g - 1].pose);
+            else write_line(g, seq, ARG_SKIP, 0, 0, nullptr);
+        }
+        publish(seq, ARG_RUN, req.kind, req.level, req.pose);
+        if (prelaunch() != GPS_OK) GPS_FAIL_LAUNCH();
+        bool got = wait_answer(seq, req.level, iter);
+        if (const int r = got ? GPS_OK : wait_late(seq, &got); r != GPS_OK) return r;
+        if (!got) return redo_plain(req, seq);
+        collect(0);
+        // The poses that rode along: their groups started with group 0's and end within a few microseconds of it.
+        // Device summer: ALWAYS waited for, needed or not -- the next launch's lines may only be written once every workgroup of
+        // this one that has pixels has delivered its row (a workgroup that finds a later line takes itself out; its group's
+        // summer would then wait for that row until ROW_TIMEOUT, with the frame stream behind it).
+        // Host-summed rows: nobody on the device waits for a row, so a pose that rode along costs the host nothing unless the
+        // loop gets to it -- its rows are waited for and added only then (answer()).
+        if (host_rows) { ride_seq = seq; return GPS_OK; }
+        for (int g = 1; g <= nc; g++) {
+            if (take(g, seq)) continue;
+            static int warned = 0;
+            if (warned < 8 && ++warned)
+                fprintf(stderr, "[gps_slam_hip] tracker: the pose riding along with evaluation %d (group %d) never answered\n", seq, g);
+            break;
+        }
+        return GPS_OK;
+    }
+    // The main wait for launch seq's answer, on the sequence number the kernel writes last -> whether it answered
+    bool wait_answer(int seq, int level, int iter) {
+        bool got = false;
+        // (diagnostic, free: the time-stamp counter around every poll tells a GPU that answered late from a host thread that
+        // was not running -- the longest gap between two consecutive polls is ~20 ns unless the thread was descheduled in between)
+        const unsigned long long tsc0 = host_cycles();
+        unsigned long long tsc_prev = tsc0, tsc_gap = 0;
+        spin_until(200000000L, [&](long spin) {
+            if (answered(0, seq)) return got = true;
+            // the launch gave up before its line arrived (this thread did not run for longer than ARG_TIMEOUT): no answer will
+            // come -- straight to the plain launch instead of spinning out the budget (rounds 3-4 did: 2 s per event)
+            if ((spin & 0xFF) == 0xFF && retired(seq)) { got = answered(0, seq); return true; }
+            const unsigned long long now = host_cycles();
+            if (now - tsc_prev > tsc_gap) tsc_gap = now - tsc_prev;
+            tsc_prev = now;
+            return false;
+        });
+        if (tsc_prev - tsc0 > 6000000ull) {  // > ~2-3 ms at 2-3 GHz: rare; say which side lost the time
+            static int said = 0;
+            if (said < 16 && ++said)
+                fprintf(stderr, "[gps_slam_hip] tracker: evaluation %d answered after %.2f Mcycles (TSC); longest gap between two "
+                                "polls of this thread %.2f Mcycles (level %d, iteration %d)\n", seq, (tsc_prev - tsc0) * 1e-6,
+                        tsc_gap * 1e-6, level, iter);
+        }
+        return got;
+    }
+    // No answer within the spin budget.  Either launch `seq` gave up before its line arrived (this thread was descheduled for
+    // longer than ARG_TIMEOUT between the launch and the publish) or it has not STARTED yet (the stream is held behind another
+    // stream's gate).  Launch seq + 1 may only be retired through the argument line once launch seq is known to have read it --
+    // otherwise seq, starting late, would never find its line and sit out ARG_TIMEOUT with the frame stream behind it.  So:
+    // leave RUN(seq) in place and wait until seq has answered after all (tags) or has retired itself (acknowledgement word).
+    int wait_late(int seq, bool* got) {
+        bool late = false, gone = false;
+        spin_until(400000000L, [&](long) { late = answered(0, seq); gone = retired(seq); return late || gone; });
+        if (!late && !gone) {
+            // Neither an answer nor a retirement (e.g. the line arrived while part of the launch's workgroups had already sat
+            // out ARG_TIMEOUT: the summer then waits for rows that never come and gives up silently).  Drain the stream instead
+            // of failing the frame: launch seq ends by one of its timeouts, the queued launch seq + 1 never finds its line and
+            // retires itself; then nobody polls the line any more and the plain launch of redo_plain() redoes the evaluation
+            // (same inputs, same fixed-order sums).
+            fprintf(stderr, "[gps_slam_hip] tracker: evaluation %d neither answered nor retired; draining the stream\n", seq);
+            if (hipStreamSynchronize(st) != hipSuccess) GPS_FAIL_LAUNCH();
+            pending = 0;
+        }
+        *got = late;
+        return GPS_OK;
+    }
+    // launch `seq` never answered: the evaluation is redone by a plain launch (whatever rode along with it is not waited for)
+    int redo_plain(const LmRequest& req, int seq) {
+        static int warned = 0;   // (rare by construction; a steady stream of these is a bug worth seeing)
+        if (warned < 8 && ++warned)
+            fprintf(stderr, "[gps_slam_hip] tracker: evaluation %d gave up waiting for its argument line; redone by a plain launch\n", seq);
+        if (pending) retire(pending);
+        pending = 0;
+        // a launch that gave up may have left the evaluation ticket partially counted and rows half delivered:
+        // both start from zero for the plain launch (the valid-pixel counts next to the ticket stay)
+        if (hipMemsetAsync(w.sync, 0, sizeof(uint32_t), st) != hipSuccess) GPS_FAIL_LAUNCH();
+        if (hipMemsetAsync(w.partial, 0, (size_t)EV_GROUPS * EV_MAX_WGS * GH_SLOTS * sizeof(uint32_t), st) != hipSuccess) GPS_FAIL_LAUNCH();
+        return eval_plain(req, mailbox);
+    }
+    // group g's answer to the last evaluation, or NULL (it did not ride along / never answered).  Host-summed rows: the rows of its
+    // group are waited for and added only now that the loop has got to it; a group that never delivers is evaluated as if
+    // nothing had ridden along.
+    const float* answer(int g) { return g < answers || (ride_seq && take(g, ride_seq)) ? raw[g] : nullptr; }
+};
 
 }  // namespace
 
@@ -1070,39 +1387,17 @@ int64_t gps_track_scratch_bytes(int width, int height) {
     return (int64_t)carve(nullptr, nullptr, width, height);
 }
 
-static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c, gps_track_state* ts, void* scratch,
-                             int64_t scratch_bytes, gps_stream stream, const int16_t* depth_mm);
 static inline double wall_ms() {
     timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
     return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
 }
 
-int gps_tsdf_track_camera(const gps_tsdf_state* sp, const gps_track_config* c, gps_track_state* ts, void* scratch,
-                          int64_t scratch_bytes, gps_stream stream) {
-    return track_camera_impl(sp, c, ts, scratch, scratch_bytes, stream, nullptr);
-}
-
-// depth_mm != NULL: s.depth has NOT been converted yet; the prepare launch does it (tile kernel) or it is converted first
-static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c, gps_track_state* ts, void* scratch,
-                             int64_t scratch_bytes, gps_stream stream, const int16_t* depth_mm) {
-    GPS_ENTER();
-    GPS_REQUIRE(sp && c && ts && scratch);
-    GPS_REQUIRE(state_valid(*sp));
-    GPS_REQUIRE(c->n_levels >= 2 && c->n_levels <= GPS_TRACK_MAX_LEVELS);
-    const TsdfState s = *sp;
+// PrepareForEvaluation: the depth pyramid (the scene side, the ICP maps, always stays at full resolution) and the per-level
+// constants of the evaluations (pa.tab_vals), in one launch
+static int launch_prepare(const gps_tsdf_state* sp, const TsdfState& s, const gps_track_config* c, gps_track_state* ts,
+                          const Scratch& w, gps_stream stream, const int16_t* depth_mm, PrepArgs& pa) {
     const int W = s.width, H = s.height;
-    GPS_REQUIRE((W >> (c->n_levels - 1)) > 0 && (H >> (c->n_levels - 1)) > 0);
-    if (scratch_bytes < gps_track_scratch_bytes(W, H)) return GPS_ERR_CAPACITY;
-    Scratch w;
-    carve(&w, (char*)scratch, W, H);
     hipStream_t st = (hipStream_t)stream;
-
-    // PrepareForEvaluation: depth pyramid; the scene side (ICP maps) always stays at full resolution
-    const float* dl[GPS_TRACK_MAX_LEVELS];
-    int lw[GPS_TRACK_MAX_LEVELS], lh[GPS_TRACK_MAX_LEVELS];
-    float lintr[GPS_TRACK_MAX_LEVELS][4] = {{s.fx, s.fy, s.cx, s.cy}};
-    dl[0] = s.depth; lw[0] = W; lh[0] = H;
-    PrepArgs pa;
     pa.cfg = *c;
     pa.depth0 = s.depth;
     pa.depth_mm = nullptr; pa.depth0_out = s.depth;
@@ -1112,11 +1407,6 @@ static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c
     }
     pa.level[0] = nullptr;
     for (int l = 1; l < GPS_TRACK_MAX_LEVELS; l++) pa.level[l] = w.level[l];
-    for (int l = 1; l < c->n_levels; l++) {
-        lw[l] = lw[l - 1] / 2; lh[l] = lh[l - 1] / 2;
-        dl[l] = w.level[l];
-        for (int k = 0; k < 4; k++) lintr[l][k] = lintr[l - 1][k] * 0.5f;
-    }
     pa.points = reinterpret_cast<const float4*>(s.icp_points);
     pa.normals = reinterpret_cast<const float4*>(s.icp_normals);
     pa.pn = w.pn; pa.W = W; pa.H = H; pa.sync = w.sync;
@@ -1134,162 +1424,39 @@ static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c
     ts->scratch_epoch = 0;  // restored on success
     pa.parity = parity;
     for (int l = 0; l < GPS_TRACK_MAX_LEVELS; l++) pa.tab_vals[l] = LevelTab{};
-    for (int l = 0; l < c->n_levels; l++)
-        pa.tab_vals[l] = LevelTab{dl[l], lw[l], lh[l], lintr[l][0], lintr[l][1], lintr[l][2], lintr[l][3], c->space_thresh[l],
-                                  min(EV_MAX_WGS, gps_div_up(lw[l] * lh[l], EV_THREADS))};
+    float intr[4] = {s.fx, s.fy, s.cx, s.cy};
+    for (int l = 0, lw = W, lh = H; l < c->n_levels; l++, lw /= 2, lh /= 2) {
+        if (l > 0)
+            for (int k = 0; k < 4; k++) intr[k] *= 0.5f;
+        pa.tab_vals[l] = LevelTab{l == 0 ? s.depth : w.level[l], lw, lh, intr[0], intr[1], intr[2], intr[3], c->space_thresh[l],
+                                  min(EV_MAX_WGS, gps_div_up(lw * lh, EV_THREADS))};
+    }
     if (c->n_levels <= 5) track_prepare_tile_kernel<<<((W + 15) >> 4) * ((H + 15) >> 4), 256, 0, st>>>(pa);
     else track_prepare_kernel<<<gps_div_up((int64_t)W * H, 4 * 256), 256, 0, st>>>(pa);
     GPS_LAUNCH_CHECK();
+    return GPS_OK;
+}
 
-    // Mailbox path: evaluations are PRE-LAUNCHED (track_eval_poll_kernel); the host's per-iteration decision is one
-    // cache-line write into the argument line (words 48..63 of the mailbox block).
-    volatile float* const mailbox = reinterpret_cast<volatile float*>(ts->host_mailbox);
-    volatile uint32_t* const arg_line = mailbox ? reinterpret_cast<volatile uint32_t*>(ts->host_mailbox) + 48 : nullptr;
-    GPS_REQUIRE(!mailbox || (reinterpret_cast<uintptr_t>(ts->host_mailbox) & 63) == 0);
-    PollArgs pl = {};
-    if (mailbox) {
-        pl.pn = w.pn; pl.sw = W; pl.sh = H;
-        pl.scene_intr = make_float4(lintr[0][0], lintr[0][1], lintr[0][2], lintr[0][3]);
-        pl.scenePose = load_mat(ts->pose_pc_M);
-        pl.tukey_cutoff = c->tukey_cutoff; pl.vf_min = s.view_frustum_min; pl.vf_max = s.view_frustum_max;
-        pl.use_weights = ts->frames_processed >= 100; pl.frames_to_skip = c->frames_to_skip; pl.frames_to_weight = c->frames_to_weight;
-        for (int l = 0; l < GPS_TRACK_MAX_LEVELS; l++) pl.tab[l] = pa.tab_vals[l];
-        pl.arg_line = const_cast<const uint32_t*>(arg_line);
-        pl.dev_line = w.dev_line;
-        pl.bar_line = reinterpret_cast<const uint32_t*>(ts->dev_arg_line);
-    }
+// depth_mm != NULL: s.depth has NOT been converted yet; the prepare launch does it (tile kernel) or it is converted first
+static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c, gps_track_state* ts, void* scratch,
+                             int64_t scratch_bytes, gps_stream stream, const int16_t* depth_mm) {
+    GPS_ENTER();
+    GPS_REQUIRE(sp && c && ts && scratch);
+    GPS_REQUIRE(state_valid(*sp));
+    GPS_REQUIRE(c->n_levels >= 2 && c->n_levels <= GPS_TRACK_MAX_LEVELS);
+    const TsdfState s = *sp;
+    const int W = s.width, H = s.height;
+    GPS_REQUIRE((W >> (c->n_levels - 1)) > 0 && (H >> (c->n_levels - 1)) > 0);
+    if (scratch_bytes < gps_track_scratch_bytes(W, H)) return GPS_ERR_CAPACITY;
+    Scratch w;
+    carve(&w, (char*)scratch, W, H);
+    hipStream_t st = (hipStream_t)stream;
+    PrepArgs pa;
+    int r = launch_prepare(sp, s, c, ts, w, stream, depth_mm, pa);
+    if (r != GPS_OK) return r;
+    GPS_REQUIRE(!ts->host_mailbox || (reinterpret_cast<uintptr_t>(ts->host_mailbox) & 63) == 0);
     GPS_REQUIRE((reinterpret_cast<uintptr_t>(ts->dev_arg_line) & 63) == 0);
-    volatile uint32_t* const bar_line = mailbox ? reinterpret_cast<volatile uint32_t*>(ts->dev_arg_line) : nullptr;
-    // (when the sequence wraps, the line of the last launch before the wrap -- a LARGER number than everything that follows -- is
-    // wiped first: a late workgroup must not mistake it for a later launch's line, see `superseded` in the kernel)
-    auto next_seq = [&]() {
-        if (ts->mail_seq >= 0x3FFFFFFF) {
-            ts->mail_seq = 0;
-            if (mailbox) mailbox[32] = 0.0f;   // (the retirement word compares like the line: `retired` below)
-            if (bar_line) {
-                for (int k = 0; k < 8 * EV_GROUPS; k++) reinterpret_cast<volatile uint64_t*>(bar_line)[k] = 0;
-                host_store_fence();
-            }
-        }
-        return (int)(++ts->mail_seq);
-    };
-    // groups of an evaluation launch: the loop's pose + the poses that ride along (BAR lines and a mailbox block per group)
-    // mailbox layout (gps_track_state.mailbox_bytes): G answer blocks of 256 bytes -- and, when there is room for them, G row tables of
-    // EV_MAX_WGS x 128 bytes behind the blocks: the workgroups then store their rows THERE and this thread adds them (host_rows)
-    constexpr int BLOCK_BYTES = MAILBOX_GROUP_WORDS * 4, ROWS_BYTES = EV_MAX_WGS * GH_SLOTS * 4;
-    static_assert(BLOCK_BYTES == GPS_TRACK_MAILBOX_BLOCK_BYTES && ROWS_BYTES == GPS_TRACK_MAILBOX_ROWS_BYTES, "include/gps_slam_hip.h");
-    const int groups_with_rows = ts->mailbox_bytes / (BLOCK_BYTES + ROWS_BYTES);
-    // (host-summed rows reproduce the device summer's bits only with IEEE float adds on this thread: with flush-to-zero or
-    // denormals-are-zero set in MXCSR -- e.g. a host built with -ffast-math that set them process-wide -- the device summer is used;
-    // round-5 advisor finding.  The 64-byte row chunks leave the device as single store instructions and are tagged in their last
-    // word; tests/test_tsdf_gpu.py keeps the host-summed == device-summed equality test in the default set)
-    const bool host_sums = mailbox && groups_with_rows >= 1 && !host_flushes_denormals();
-    const int mailbox_groups = host_sums ? groups_with_rows : ts->mailbox_bytes >= 2 * BLOCK_BYTES ? ts->mailbox_bytes / BLOCK_BYTES : 1;
-    const int n_groups = (mailbox && bar_line) ? max(1, min(EV_GROUPS, mailbox_groups)) : 1;
-    volatile uint32_t* const host_rows = host_sums ? reinterpret_cast<volatile uint32_t*>(ts->host_mailbox) + (size_t)min(EV_GROUPS, mailbox_groups) * MAILBOX_GROUP_WORDS : nullptr;
-    pl.host_rows = host_rows;
-    // The answer of group g to launch `seq`: the summer's block, or -- host_rows -- the rows of its table added in the summer's order
-    // (thread (r, k) of the summer adds word k of rows r, r + 8, ... in increasing order, then the eight partial sums in order:
-    // eval_fused / sum_rows_and_answer; IEEE additions only, so the bits are the device's).  `next` remembers the first row not yet
-    // seen: rows are stable once tagged (nothing rewrites them before the next launch's lines are published).
-    // Rows are added AS THEY ARRIVE (in row order: the scan below only ever moves forward), so that the last row to land costs one
-    // row's additions, not a pass over the table.
-    int rows_next[EV_GROUPS] = {0};
-    float rows_part[EV_GROUPS][EV_ROW_GROUPS][GH_SLOTS];
-    auto rows_reset = [&](int g) {
-        rows_next[g] = 0;
-        for (int q = 0; q < EV_ROW_GROUPS; q++)
-            for (int k = 0; k < GH_SLOTS; k++) rows_part[g][q][k] = 0.0f;
-    };
-    auto answered = [&](int g, int seq, int n_rows) -> bool {
-        if (!host_rows) {
-            volatile float* const mb = mailbox + g * MAILBOX_GROUP_WORDS;
-            return float_bits(mb[15]) == seq && float_bits(mb[31]) == seq;
-        }
-        volatile uint32_t* const T = host_rows + (size_t)g * EV_MAX_WGS * GH_SLOTS;
-        int& r = rows_next[g];
-        while (r < n_rows && (int)T[r * GH_SLOTS + 15] == seq && (int)T[r * GH_SLOTS + 31] == seq) {
-            float* dst = rows_part[g][r % EV_ROW_GROUPS];
-            for (int k = 0; k < GH_SLOTS; k++) {
-                if ((k & 15) == 15) continue;   // the row's tags
-                const uint32_t v = T[r * GH_SLOTS + k]; float f; memcpy(&f, &v, 4); dst[k] += f;
-            }
-            r++;
-        }
-        return r >= n_rows;
-    };
-    auto collect = [&](int g, int n_rows, float* raw /* GH_SLOTS words, chunked like a row */) {
-        if (!host_rows) {
-            volatile float* const mb = mailbox + g * MAILBOX_GROUP_WORDS;
-            for (int k = 0; k < GH_SLOTS; k++) raw[k] = mb[k];
-            return;
-        }
-        (void)n_rows;   // (answered(g) has added every row)
-        volatile uint32_t* const T = host_rows + (size_t)g * EV_MAX_WGS * GH_SLOTS;
-        for (int k = 0; k < GH_SLOTS; k++) {
-            float t = 0.0f;
-            for (int q = 0; q < EV_ROW_GROUPS; q++) t += rows_part[g][q][k];
-            raw[k] = t;
-        }
-        const uint32_t vcount = T[30];   // payload 29 of row 0: the frame's valid-pixel count (bits)
-        memcpy(&raw[30], &vcount, 4);
-    };
-    // One argument line: payload first, sequence number last (x86 stores are not reordered with each other; the compiler barrier
-    // keeps the order).  Group g's line sits 64 bytes behind group g - 1's in the BAR block; the pinned line has group 0 only.
-    auto write_line = [&](int grp, int seq, uint32_t cmd, int kind, int level, const float* pose) {
-        uint32_t wds[16] = {0};
-        wds[1] = cmd | ((uint32_t)kind << 8) | ((uint32_t)level << 16);
-        if (pose)
-            for (int col = 0; col < 4; col++)
-                for (int r = 0; r < 3; r++) memcpy(&wds[2 + col * 3 + r], &pose[col * 4 + r], 4);
-        wds[0] = (uint32_t)seq;
-        uint32_t x = 0;
-        for (int k = 0; k < 15; k++) x ^= wds[k];
-        wds[15] = x;
-        if (bar_line) {
-            // through the BAR: the mapping is write-combining, so the 64 bytes gather in one of the core's WC buffers and leave
-            // as one posted write when the sfence drains it (without the fence the line sits there until something evicts
-            // it: tools/probe/pingpong.hip reads 560 us per round trip instead of 1.8).  A torn line fails the xor word.
-            volatile uint64_t* dst = reinterpret_cast<volatile uint64_t*>(bar_line + 16 * grp);
-            for (int k = 0; k < 16; k += 2) dst[k >> 1] = (uint64_t)wds[k] | ((uint64_t)wds[k + 1] << 32);
-            return;
-        }
-        for (int k = 1; k < 16; k++) arg_line[k] = wds[k];
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        arg_line[0] = wds[0];
-    };
-    // group 0's line, then the fence that sends every line written since the last one on its way
-    auto publish = [&](int seq, uint32_t cmd, int kind, int level, const float* pose) {
-        write_line(0, seq, cmd, kind, level, pose);
-        if (bar_line) host_store_fence();
-    };
-    // Retire a pre-launched evaluation the loop did not need: ARG_SKIP, then wait until the launch has SEEN it (mailbox word
-    // 32 := its sequence number).  Usually that launch is already polling and answers within a PCIe round trip; when it is
-    // still queued behind other streams' kernels the wait is what keeps the next frame's first arguments from overwriting the
-    // line it has yet to read (measured without it: 1 overlap run in ~10 lost 50 ms -- one ARG_TIMEOUT -- in a single frame).
-    // launch `seq` -- or a later one, which cannot have started before `seq` had drained -- has taken itself out (ARG_SKIP or its
-    // own ARG_TIMEOUT) and said so in mailbox word 32
-    auto retired = [&](int seq) -> bool { return (int32_t)((uint32_t)float_bits(mailbox[32]) - (uint32_t)seq) >= 0; };
-    auto retire = [&](int seq) {
-        for (int g = 1; g < n_groups; g++) write_line(g, seq, ARG_SKIP, 0, 0, nullptr);
-        publish(seq, ARG_SKIP, 0, 0, nullptr);
-        for (long spin = 0; spin < 400000000L; spin++) {  // (bounded; the launch gives up by itself after ARG_TIMEOUT)
-            if (retired(seq)) break;
-            if ((spin & 0xFFFF) == 0xFFFF) sched_yield();
-        }
-    };
-    // a pre-launched evaluation that has not been given its arguments yet; retired on every way out
-    struct Pending {
-        int seq = 0;
-        decltype(retire)* ret;
-        ~Pending() { if (seq) (*ret)(seq); }
-    } pending;
-    pending.ret = &retire;
-    auto prelaunch = [&]() -> int {
-        pending.seq = next_seq();
-        track_eval_poll_kernel<<<n_groups * EV_MAX_WGS, EV_THREADS, 0, st>>>(pl, w.partial, w.sync, w.result, mailbox, pending.seq, parity);
-        return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
-    };
+    Handover ho(s, c, ts, w, st, pa);
 
     // The LM loop.  An evaluation is handed the loop's next pose AND (BAR line + a mailbox with room for the answers,
     // gps_track_state.mailbox_bytes) the poses the loop would evaluate after it if it is rejected: a rejection reads nothing of
@@ -1301,211 +1468,53 @@ static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c
     lm.start(c, ts->pose_M, ts->pose_invM);
     int eval_launches = 0, spec_issued = 0, spec_used = 0;
     for (int k = 0; k < 16; k++) ts->diag[k] = 0;
-    const int use_weights = ts->frames_processed >= 100;
-
     while (lm.active) {
         const LmRequest req = lm.request();
-        const int level = req.level, it = req.kind;
         LmRequest cand[EV_GROUPS];
-        int nc = 0;
-        // (the first evaluation of a level is only rejected when it has no valid pixel at all: nothing rides along with it)
-        if (n_groups > 1 && lm.iter > 0) {
-            LmLoop sim = lm;
-            while (nc < n_groups - 1) {
-                sim.apply(nullptr);
-                if (!sim.active) break;
-                cand[nc++] = sim.request();
-            }
-        }
-        GhArgs a;
-        a.depth = dl[level]; a.vw = lw[level]; a.vh = lh[level];
-        a.view_intr = make_float4(lintr[level][0], lintr[level][1], lintr[level][2], lintr[level][3]);
-        a.pn = w.pn;
-        a.sw = W; a.sh = H;
-        a.scene_intr = make_float4(lintr[0][0], lintr[0][1], lintr[0][2], lintr[0][3]);
-        a.approxInvPose = load_mat(req.pose); a.scenePose = load_mat(ts->pose_pc_M);
-        a.space_thresh = c->space_thresh[level]; a.tukey_cutoff = c->tukey_cutoff; a.vf_min = s.view_frustum_min;
-        a.vf_max = s.view_frustum_max; a.use_weights = use_weights; a.frames_to_skip = c->frames_to_skip;
-        a.frames_to_weight = c->frames_to_weight;
-        const int n_wgs = min(EV_MAX_WGS, gps_div_up(a.vw * a.vh, EV_THREADS));
-        float raw[EV_GROUPS][GH_SLOTS];  // per group two 64-byte chunks: 15 payload words + the sequence number each (eval_body)
-        int answers = 1;                 // raw[0 .. answers) hold results: the evaluation itself, then the poses that rode along
-        int ride_seq = 0;                // host-summed rows: the launch whose riding-along groups may still be collected (0: none)
-        if (mailbox) {
-            // this evaluation is the pre-launched kernel (or the frame's first launch): hand it its arguments, then put
-            // the NEXT evaluation on the stream before waiting -- its launch cost overlaps this evaluation
-            if (!pending.seq && prelaunch() != GPS_OK) GPS_FAIL_LAUNCH();
-            const int seq = pending.seq;
-            pending.seq = 0;
-            for (int g = 0; g < n_groups; g++) {   // per-state sequence numbers (>= 1): nothing stale can match
-                mailbox[g * MAILBOX_GROUP_WORDS + 15] = 0.0f; mailbox[g * MAILBOX_GROUP_WORDS + 31] = 0.0f;
-                rows_reset(g);
-            }
-            for (int g = 1; g < n_groups; g++) {
-                if (g <= nc) write_line(g, seq, ARG_RUN, cand[g - 1].kind, cand[g - 1].level, cand[g - 1].pose);
-                else write_line(g, seq, ARG_SKIP, 0, 0, nullptr);
-            }
-            publish(seq, ARG_RUN, it, level, req.pose);
-            eval_launches++;
-            spec_issued += nc;
-            if (prelaunch() != GPS_OK) GPS_FAIL_LAUNCH();
-            // spin on the sequence number the kernel writes last (bounded)
-            bool got = false, by_mailbox = true;
-            // (diagnostic, free: the time-stamp counter around every poll tells a GPU that answered late from a host
-            // thread that was not running -- the longest gap between two consecutive polls is ~20 ns unless the thread
-            // was descheduled in between)
-            const unsigned long long tsc0 = host_cycles();
-            unsigned long long tsc_prev = tsc0, tsc_gap = 0;
-            for (long spin = 0; spin < 200000000L; spin++) {
-                if (answered(0, seq, n_wgs)) { got = true; break; }
-                // the launch gave up before its line arrived (this thread did not run for longer than ARG_TIMEOUT): no answer will
-                // come -- straight to the plain launch below instead of spinning out the budget (rounds 3-4 did: 2 s per event)
-                if ((spin & 0xFF) == 0xFF && retired(seq)) { got = answered(0, seq, n_wgs); break; }
-                const unsigned long long now = host_cycles();
-                if (now - tsc_prev > tsc_gap) tsc_gap = now - tsc_prev;
-                tsc_prev = now;
-                // a result normally lands within ~20 us (a few thousand polls); a host that is still spinning far beyond
-                // that is oversubscribed or the GPU is busy elsewhere: stop burning the core between polls
-                if ((spin & 0xFFFF) == 0xFFFF) sched_yield();
-            }
-            if (tsc_prev - tsc0 > 6000000ull) {  // > ~2-3 ms at 2-3 GHz: rare; say which side lost the time
-                static int said = 0;
-                if (said < 16 && ++said)
-                    fprintf(stderr, "[gps_slam_hip] tracker: evaluation %d answered after %.2f Mcycles (TSC); longest gap between two "
-                                    "polls of this thread %.2f Mcycles (level %d, iteration %d)\n", seq, (tsc_prev - tsc0) * 1e-6,
-                            tsc_gap * 1e-6, level, lm.iter);
-            }
-            if (!got) {
-                // No answer within the spin budget.  Either launch `seq` gave up before its line arrived (this thread was
-                // descheduled for longer than ARG_TIMEOUT between the launch and the publish) or it has not STARTED yet (the
-                // stream is held behind another stream's gate).  Launch seq + 1 may only be retired through the argument line
-                // once launch seq is known to have read it -- otherwise seq, starting late, would never find its line and sit
-                // out ARG_TIMEOUT with the frame stream behind it.  So: leave RUN(seq) in place and wait until seq has answered
-                // after all (tags) or has retired itself (acknowledgement word).
-                bool late = false, gone = false;
-                for (long spin = 0; spin < 400000000L && !late && !gone; spin++) {
-                    late = answered(0, seq, n_wgs);
-                    gone = retired(seq);
-                    if ((spin & 0xFFFF) == 0xFFFF) sched_yield();
-                }
-                if (!late && !gone) {
-                    // Neither an answer nor a retirement (e.g. the line arrived while part of the launch's workgroups had
-                    // already sat out ARG_TIMEOUT: the summer then waits for rows that never come and gives up silently).
-                    // Drain the stream instead of failing the frame: launch seq ends by one of its timeouts, the queued
-                    // launch seq + 1 never finds its line and retires itself; then nobody polls the line any more and the
-                    // plain launch below redoes the evaluation (same inputs, same fixed-order sums).
-                    fprintf(stderr, "[gps_slam_hip] tracker: evaluation %d neither answered nor retired; draining the stream\n", seq);
-                    if (hipStreamSynchronize(st) != hipSuccess) GPS_FAIL_LAUNCH();
-                    pending.seq = 0;
-                }
-                got = late;
-            }
-            if (!got) {
-                static int warned = 0;   // (rare by construction; a steady stream of these is a bug worth seeing)
-                if (warned < 8 && ++warned)
-                    fprintf(stderr, "[gps_slam_hip] tracker: evaluation %d gave up waiting for its argument line; redone by a plain launch\n", seq);
-                if (pending.seq) retire(pending.seq);
-                pending.seq = 0;
-                // a launch that gave up may have left the evaluation ticket partially counted and rows half delivered:
-                // both start from zero for the plain launch (the valid-pixel counts next to the ticket stay)
-                if (hipMemsetAsync(w.sync, 0, sizeof(uint32_t), st) != hipSuccess) GPS_FAIL_LAUNCH();
-                if (hipMemsetAsync(w.partial, 0, (size_t)EV_GROUPS * EV_MAX_WGS * GH_SLOTS * sizeof(uint32_t), st) != hipSuccess) GPS_FAIL_LAUNCH();
-                const int seq2 = next_seq();
-                if (it == TRK_ROTATION) track_eval_kernel<TRK_ROTATION><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, mailbox, seq2, parity);
-                else if (it == TRK_TRANSLATION) track_eval_kernel<TRK_TRANSLATION><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, mailbox, seq2, parity);
-                else track_eval_kernel<TRK_BOTH><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, mailbox, seq2, parity);
-                GPS_LAUNCH_CHECK();
-                if (hipStreamSynchronize(st) != hipSuccess || float_bits(mailbox[15]) != seq2 || float_bits(mailbox[31]) != seq2)
-                    GPS_FAIL_LAUNCH();
-                by_mailbox = false;   // (whatever rode along with launch seq is not waited for)
-            }
-            if (by_mailbox) collect(0, n_wgs, raw[0]);
-            else for (int k = 0; k < GH_SLOTS; k++) raw[0][k] = mailbox[k];   // (the plain launch's summer wrote the block)
-            // The poses that rode along: their groups started with group 0's and end within a few microseconds of it.
-            // Device summer: ALWAYS waited for, needed or not -- the next launch's lines may only be written once every workgroup of
-            // this one that has pixels has delivered its row (a workgroup that finds a later line takes itself out; its group's
-            // summer would then wait for that row until ROW_TIMEOUT, with the frame stream behind it).
-            // Host-summed rows: nobody on the device waits for a row, so a pose that rode along costs the host nothing unless the
-            // loop gets to it -- its rows are waited for and added only then (ride_seq below).
-            for (int g = 1; by_mailbox && !host_rows && g <= nc; g++) {
-                const int lg = cand[g - 1].level;
-                const int n_wgs_g = min(EV_MAX_WGS, gps_div_up(lw[lg] * lh[lg], EV_THREADS));
-                bool have = false;
-                for (long spin = 0; spin < 200000000L; spin++) {
-                    if (answered(g, seq, n_wgs_g)) { have = true; break; }
-                    if ((spin & 0xFFFF) == 0xFFFF) sched_yield();
-                }
-                if (!have) {
-                    static int warned2 = 0;
-                    if (warned2 < 8 && ++warned2)
-                        fprintf(stderr, "[gps_slam_hip] tracker: the pose riding along with evaluation %d (group %d) never answered\n", seq, g);
-                    break;
-                }
-                collect(g, n_wgs_g, raw[g]);
-                answers = g + 1;
-            }
-            if (by_mailbox && host_rows) ride_seq = seq;
-        } else {
-            const int seq = next_seq();
-            if (it == TRK_ROTATION) track_eval_kernel<TRK_ROTATION><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, nullptr, seq, parity);
-            else if (it == TRK_TRANSLATION) track_eval_kernel<TRK_TRANSLATION><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, nullptr, seq, parity);
-            else track_eval_kernel<TRK_BOTH><<<n_wgs, EV_THREADS, 0, st>>>(a, w.partial, w.sync, w.result, nullptr, seq, parity);
-            GPS_LAUNCH_CHECK();
-            eval_launches++;
-            // the reference's GPU tracker reads its 32 accumulators back every iteration as well
-            if (hipMemcpyAsync(raw[0], w.result, sizeof(raw[0]), hipMemcpyDeviceToHost, st) != hipSuccess) GPS_FAIL_LAUNCH();
-            if (hipStreamSynchronize(st) != hipSuccess) GPS_FAIL_LAUNCH();
-            if (float_bits(raw[0][15]) != seq || float_bits(raw[0][31]) != seq) GPS_FAIL_LAUNCH();  // the summer gave up
-        }
+        const int nc = lm.rejection_chain(ho.n_groups - 1, cand);
+        if ((r = ho.evaluate(req, cand, nc, lm.iter)) != GPS_OK) return r;
+        eval_launches++;
+        spec_issued += nc;
         // the loop's decision on the evaluation -- and, while it keeps rejecting, on the poses that rode along with it
         bool rejected = true;
-        for (int g = 0; g < (ride_seq ? nc + 1 : answers) && rejected && lm.active; g++) {
-            if (g > 0) {
-                if (!lm.request().same(cand[g - 1])) break;   // (cannot happen: the same arithmetic on the same state)
-                if (ride_seq) {   // the rows of this pose's group: waited for and added only now that the loop has got to it
-                    const int lg = cand[g - 1].level;
-                    const int n_wgs_g = min(EV_MAX_WGS, gps_div_up(lw[lg] * lh[lg], EV_THREADS));
-                    bool have = false;
-                    for (long spin = 0; spin < 200000000L; spin++) {
-                        if (answered(g, ride_seq, n_wgs_g)) { have = true; break; }
-                        if ((spin & 0xFFFF) == 0xFFFF) sched_yield();
-                    }
-                    if (!have) break;   // (its group never delivered: the loop evaluates the pose itself, as if nothing had ridden along)
-                    collect(g, n_wgs_g, raw[g]);
-                }
-                spec_used++;
-            }
+        for (int g = 0; g <= nc && rejected && lm.active; g++) {
+            if (g > 0 && !lm.request().same(cand[g - 1])) break;   // (cannot happen: the same arithmetic on the same state)
+            const float* raw = ho.answer(g);
+            if (!raw) break;
+            if (g > 0) spec_used++;
             float host[GH_SLOTS];
-            for (int d = 0; d < 30; d++) host[d] = raw[g][d + d / 15];  // payload d lives in word d + d / 15
+            for (int d = 0; d < 30; d++) host[d] = raw[d + d / 15];  // payload d lives in word d + d / 15
             rejected = lm.apply(host);
             if (lm.bad_pose) return GPS_ERR_ARG;
         }
     }
-    const int n_valid_bits = lm.n_valid_bits, last_type = lm.last_type, nvalid_depth_good = lm.nvalid_depth_good;
-    const float f_depth_good = lm.f_depth_good;
-    const float *M = lm.M, *invM = lm.invM, *hessian_depth_good = lm.hessian_depth_good;
     for (int l = 0; l < GPS_TRACK_MAX_LEVELS && l < 8; l++) ts->diag[l] = (float)lm.evals[l];
     ts->diag[12] = (float)spec_issued; ts->diag[13] = (float)spec_used;   // poses that rode along / that the loop then consumed
-    memcpy(ts->pose_M, M, 64); memcpy(ts->pose_invM, invM, 64);
+    memcpy(ts->pose_M, lm.M, 64); memcpy(ts->pose_invM, lm.invM, 64);
     // UpdatePoseQuality: the residual score (the SVM verdict only feeds failure modes that are off by default,
     // ITMLibSettings.cpp:42 behaviourOnFailure = FAILUREMODE_IGNORE)
     int n_max = 0;
     if (eval_launches > 0) {
-        n_max = n_valid_bits;  // delivered with every evaluation's sums
+        n_max = lm.n_valid_bits;  // delivered with every evaluation's sums
     } else {
         int slots[VC_SLOTS];
-        if (hipMemcpyAsync(slots, w.sync + VC_BASE + parity * VC_SLOTS, sizeof(slots), hipMemcpyDeviceToHost, st) != hipSuccess) GPS_FAIL_LAUNCH();
+        if (hipMemcpyAsync(slots, w.sync + VC_BASE + pa.parity * VC_SLOTS, sizeof(slots), hipMemcpyDeviceToHost, st) != hipSuccess) GPS_FAIL_LAUNCH();
         if (hipStreamSynchronize(st) != hipSuccess) GPS_FAIL_LAUNCH();
         for (int k = 0; k < VC_SLOTS; k++) n_max += slots[k];
     }
-    ts->diag[8] = (float)nvalid_depth_good; ts->diag[9] = f_depth_good;
-    ts->diag[10] = n_max > 0 ? sqrtf(((float)nvalid_depth_good * f_depth_good + (float)(n_max - nvalid_depth_good) * c->space_thresh[0]) /
-                                    (float)n_max) : 0.0f;
+    const int nvalid = lm.nvalid_depth_good; const float f = lm.f_depth_good;
+    ts->diag[8] = (float)nvalid; ts->diag[9] = f;
+    ts->diag[10] = n_max > 0 ? sqrtf(((float)nvalid * f + (float)(n_max - nvalid) * c->space_thresh[0]) / (float)n_max) : 0.0f;
     float det = 0.0f;
-    if (last_type == TRK_BOTH) { det = Chol(hessian_depth_good, 6).determinant(); if (isnan(det)) det = 0.0f; }
+    if (lm.last_type == TRK_BOTH) { det = Chol(lm.hessian_depth_good, 6).determinant(); if (isnan(det)) det = 0.0f; }
     ts->diag[11] = det;
-    if (eval_launches > 0) ts->scratch_epoch = 2 - parity;  // 1 + the other parity (its slot was cleared by those launches)
+    if (eval_launches > 0) ts->scratch_epoch = 2 - pa.parity;  // 1 + the other parity (its slot was cleared by those launches)
     return GPS_OK;
+}
+
+int gps_tsdf_track_camera(const gps_tsdf_state* sp, const gps_track_config* c, gps_track_state* ts, void* scratch,
+                          int64_t scratch_bytes, gps_stream stream) {
+    return track_camera_impl(sp, c, ts, scratch, scratch_bytes, stream, nullptr);
 }
 
 int gps_tsdf_process_frame_tracked(const gps_tsdf_state* s, const int16_t* depth_mm, const gps_track_config* cfg,
