@@ -4,6 +4,7 @@
 
 #include <chrono>
 #include <cstdlib>
+#include <deque>
 
 #include <c10/hip/HIPCachingAllocator.h>
 #include <c10/hip/HIPGuard.h>
@@ -15,7 +16,15 @@ using namespace gpsh;
 
 namespace {
 inline void hip_ok(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e)); }
-struct MapStream { c10::hip::HIPStream s; };
+// an event that orders streams (no timing), owned
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() { hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate"); }
+    ~Event() { (void)hipEventDestroy(ev); }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    operator hipEvent_t() const { return ev; }
+};
 // kind 0 / 1: torch's high- / normal-priority pool; 2 / 3 / 4: a stream of this library's own (hipStreamCreateWithPriority,
 // non-blocking) at the lowest / highest / default priority, wrapped for the stream guards.  ONE stream per (device, kind) for the
 // life of the process, shared by every pipeline: ROCm places a new stream on a hardware queue by what exists at that moment, and
@@ -49,6 +58,31 @@ c10::hip::HIPStream make_stream(int kind) {
 }  // namespace
 using torch::indexing::Slice;
 
+// The overlapped schedules' streams (see make_stream: handles on the process-wide streams) and the fixed events between them.
+struct SLAMPipeline::Streams {
+    c10::hip::HIPStream map, frame;
+    Event frame_fused;   // "frame i is fused": what an update's raycasts wait for
+    Event raycasts;      // "the update's raycasts have read the volume": the gate of the next frame's fusion
+    Event map_done;      // streams-only schedule: the update's last iteration
+    Event caller;        // the caller's stream at processFrame (inputs)
+    Event job[2][2];     // {window batch, keyframe batch} per update parity, for the views the frame thread enqueues
+    Streams(int map_kind, int frame_kind) : map(make_stream(map_kind)), frame(make_stream(frame_kind)) {}
+    ~Streams() { (void)hipStreamSynchronize(map.stream()); (void)hipStreamSynchronize(frame.stream()); }
+};
+
+struct SLAMPipeline::RaycastStream {
+    c10::hip::HIPStream s;
+    Event begin;                // "the volume the raycasts read is complete" (recorded on the issuing stream)
+    std::deque<Event> pool;     // one per raycast batch of the current update, reused by the next
+    size_t next = 0;
+    explicit RaycastStream(int kind) : s(make_stream(kind)) {}
+    ~RaycastStream() { (void)hipStreamSynchronize(s.stream()); }
+    hipEvent_t nextEvent() {
+        if (next == pool.size()) pool.emplace_back();
+        return pool[next++];
+    }
+};
+
 unsigned long long getGPUMemoryUsage(int gpu_id) {
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess) return ~0ull;
@@ -77,6 +111,8 @@ SLAMPipeline::SLAMPipeline(TsdfEngine* tsdf_engine, SLAMGaussianModel* model_, u
 SLAMPipeline::SLAMPipeline(uint64_t seed) : rng_kf_(seed ^ 0x9E3779B97F4A7C15ull), rng_(seed), gen_(at::detail::createCPUGenerator(seed)) {}
 
 void SLAMPipeline::setTsdfEngine(InfiniTAM::Engine::CLIEngine* engine) {
+    // an engine attached before must not call back into this pipeline (its Shutdown() would detach the new one)
+    detachTsdfEngine();
     tsdf_engine = engine;
     auto* be = dynamic_cast<ITMLib::ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(engine->getMainEngine());
     TORCH_CHECK(be != nullptr, "setTsdfEngine: the main engine must be an ITMBasicEngine<ITMVoxel, ITMVoxelIndex>");
@@ -96,12 +132,14 @@ void SLAMPipeline::detachTsdfEngine() {
     tsdf_engine = nullptr;
 }
 
+void SLAMPipeline::requireEngine(const char* who) const {
+    TORCH_CHECK(main_engine != nullptr, who, ": no TSDF engine is attached -- it was shut down (CLIEngine::Shutdown / detachTsdfEngine) or "
+                "never set; attach one with setTsdfEngine()");
+}
+
 static inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-// host time the frame thread spent WAITING for the map worker inside the last processFrame call: for the previous update to finish
-// (hand-over at a keyframe) and for this update's raycasts to be enqueued (gate of the next frame's fusion)
-static thread_local double g_gate_wait_ms = 0.0, g_handover_wait_ms = 0.0;
 
 // slam_pipeline.cpp:52-173 with its LOG_PIPELINE_TIME clock: `times` holds what the reference prints as "[PIPELINE AVG TIME]"
 void SLAMPipeline::SLAMTrainCams(SLAMGaussianModel& model_, std::vector<Camera>& cams) {
@@ -114,7 +152,7 @@ void SLAMPipeline::SLAMTrainCams(SLAMGaussianModel& model_, std::vector<Camera>&
         const double tf = now_ms();
         processFrame((int)i, cams[i]);
         const double dt = now_ms() - tf;
-        if (keep_frame_ms) { frame_ms.push_back((float)dt); frame_wait_ms.push_back((float)(g_gate_wait_ms + g_handover_wait_ms)); }
+        if (keep_frame_ms) { frame_ms.push_back((float)dt); frame_wait_ms.push_back((float)(gate_wait_ms_ + handover_wait_ms_)); }
         if (i >= 30 && dt > times.max_frame_after_30) { times.max_frame_after_30 = dt; times.max_frame_id = (int)i; }
     }
     flush();
@@ -125,25 +163,21 @@ void SLAMPipeline::SLAMTrainCams(SLAMGaussianModel& model_, std::vector<Camera>&
     // slam_pipeline.cpp:168-171: emptyCache(), then the device memory in use (what run/read_results.py reads as "GPU memory usage")
     c10::hip::HIPCachingAllocator::emptyCache();
     times.gpu_memory_mb = (long long)getGPUMemoryUsage((int)c10::hip::current_device());
-    if (log_pipeline_time) {
-        if (FILE* f = fopen((workspace_dir + "/time_log.txt").c_str(), "w")) {   // (the file run/read_results.py parses)
-            fprintf(f, "[PIPELINE AVG TIME] GS num: %d, per frame fusion time: %f, localFrameRaycast time: %f, keyFrameRaycast time: %f, "
-                       "initNewGaussians time: %f, localOptimize time: %f, FPS: %f\n", model->getGaussianNum(), times.per_frame / times.frames,
-                    times.localFrameRaycast / times.frames, times.keyFrameRaycast / times.frames, times.initNewGaussians / times.frames,
-                    times.localOptimize / times.frames, times.fps());
-            fprintf(f, "GPU memory usage: %d MB\n", (int)times.gpu_memory_mb);
-            fclose(f);
-        }
-        printf("GPU memory usage: %d MB\n", (int)times.gpu_memory_mb);
+    if (!log_pipeline_time) return;
+    char avg[512];
+    snprintf(avg, sizeof avg, "[PIPELINE AVG TIME] GS num: %d, per frame fusion time: %f, localFrameRaycast time: %f, keyFrameRaycast time: %f, "
+             "initNewGaussians time: %f, localOptimize time: %f, FPS: %f\n", model->getGaussianNum(), times.per_frame / times.frames,
+             times.localFrameRaycast / times.frames, times.keyFrameRaycast / times.frames, times.initNewGaussians / times.frames,
+             times.localOptimize / times.frames, times.fps());
+    if (FILE* f = fopen((workspace_dir + "/time_log.txt").c_str(), "w")) {   // (the file run/read_results.py parses)
+        fprintf(f, "%sGPU memory usage: %d MB\n", avg, (int)times.gpu_memory_mb);
+        fclose(f);
     }
-    if (log_pipeline_time)
-        printf("[PIPELINE AVG TIME] GS num: %d, per frame fusion time: %f, localFrameRaycast time: %f, keyFrameRaycast time: %f, "
-               "initNewGaussians time: %f, localOptimize time: %f, FPS: %f\n", model->getGaussianNum(), times.per_frame / times.frames,
-               times.localFrameRaycast / times.frames, times.keyFrameRaycast / times.frames, times.initNewGaussians / times.frames,
-               times.localOptimize / times.frames, times.fps());
+    printf("GPU memory usage: %d MB\n%s", (int)times.gpu_memory_mb, avg);
 }
 
 void SLAMPipeline::processFrame(int i, Camera& cam) {
+    requireEngine("processFrame(i, cam)");
     TORCH_CHECK(tsdf_engine != nullptr && model != nullptr, "processFrame(i, cam): setTsdfEngine() and a model first");
     processFrame(i, cam, torch::Tensor(), torch::Tensor());
 }
@@ -175,6 +209,7 @@ void SLAMPipeline::loadConfig(const Config& c) {
 
 // ------------------------------------------------------------------ raycast -> tensors (runRaycastByCam :362-415)
 TensorDict SLAMPipeline::runRaycastByCam(const Camera& cam, bool use_cam_depth) {
+    requireEngine("runRaycastByCam");
     TensorDict m = raycastCam(cam, main_engine->camPoses);
     if (use_cam_depth) {  // slam_pipeline.cpp:405-408: the sensor depth instead of the raycast's (no call site of the loop uses it)
         TORCH_CHECK(cam.depth.defined(), "runRaycastByCam(use_cam_depth = true): the camera has no depth image");
@@ -193,107 +228,63 @@ static ITMLib::ITMIntrinsics intrinsicsOf(const Camera& cam, const TsdfEngine* e
     return in;
 }
 
-TensorDict SLAMPipeline::raycastCam(const Camera& cam, const std::vector<ORUtils::SE3Pose>& poses, void** ev_out) {
-    TsdfEngine* eng = main_engine;
-    if (ev_out && !rc_stream_) beginAsyncRaycasts();  // (a caller that skipped localFrameRaycast: order the raycast stream now)
+// the pose a camera is rendered with: the engine's own for a frame of the sequence, else the camera's c2w
+static ORUtils::SE3Pose poseOf(const Camera& cam, const std::vector<ORUtils::SE3Pose>& poses) {
+    if (cam.id >= 0 && cam.id < (int)poses.size()) return poses[cam.id];
     ORUtils::SE3Pose pose;
-    if (cam.id >= 0 && cam.id < (int)poses.size()) {
-        pose = poses[cam.id];
-    } else {
-        auto c = cam.c2w.to(torch::kCPU, torch::kFloat32).contiguous();
-        pose.SetInvM(c.data_ptr<float>());
-        pose.Coerce();
-    }
-    const int H = cam.height, W = cam.width;
-    const auto F = f32(device);
-    // (the result tensors are allocated on the CONSUMER's stream, before the guard below: the caching allocator ties a block
-    // to the stream that was current at allocation)
+    auto c = cam.c2w.to(torch::kCPU, torch::kFloat32).contiguous();
+    pose.SetInvM(c.data_ptr<float>());
+    pose.Coerce();
+    return pose;
+}
+
+// the five result tensors of one view, from `alloc(h, w, channels)`
+template <class Alloc>
+static TensorDict resultMaps(const Camera& cam, Alloc&& alloc) {
     TensorDict m;
-    m["color_map"] = torch::empty({H, W, 3}, F);
-    m["vertex_map"] = torch::empty({H, W, 3}, F);
-    m["confidence_map"] = torch::empty({H, W, 1}, F);
-    m["depth_map"] = torch::empty({H, W, 1}, F);
-    m["depth_map_clamped"] = torch::empty({H, W, 1}, F);
+    m["color_map"] = alloc(cam.height, cam.width, 3);
+    m["vertex_map"] = alloc(cam.height, cam.width, 3);
+    m["confidence_map"] = alloc(cam.height, cam.width, 1);
+    m["depth_map"] = alloc(cam.height, cam.width, 1);
+    m["depth_map_clamped"] = alloc(cam.height, cam.width, 1);
+    return m;
+}
+
+TensorDict SLAMPipeline::raycastCam(const Camera& cam, const std::vector<ORUtils::SE3Pose>& poses) {
+    requireEngine("raycast");
+    TsdfEngine* eng = main_engine;
+    ORUtils::SE3Pose pose = poseOf(cam, poses);
+    const auto F = f32(device);
+    TensorDict m = resultMaps(cam, [&](int64_t h, int64_t w, int64_t c) { return torch::empty({h, w, c}, F); });
     auto w2c = poseInv(cam.c2w.to(torch::kCPU, torch::kFloat32)).contiguous();  // poseInv(cam.c2w): dataset pose (:398)
-    c10::optional<c10::hip::HIPStreamGuard> on_rc;
-    if (ev_out) on_rc.emplace(static_cast<MapStream*>(rc_stream_)->s);
     ITMLib::ITMIntrinsics intr = intrinsicsOf(cam, eng);
     eng->runRaycast(&pose, &intr);
-    check(gps_raycast_to_maps(W, H, reinterpret_cast<const float*>(eng->GetFreeVertex()->GetData(MEMORYDEVICE_CUDA)),
+    check(gps_raycast_to_maps(cam.width, cam.height, reinterpret_cast<const float*>(eng->GetFreeVertex()->GetData(MEMORYDEVICE_CUDA)),
                               reinterpret_cast<const uint8_t*>(eng->GetFreeImage()->GetData(MEMORYDEVICE_CUDA)),
                               eng->getVoxelSize(), w2c.data_ptr<float>(), fptr(m["color_map"]), fptr(m["vertex_map"]),
                               fptr(m["confidence_map"]), fptr(m["depth_map"]), fptr(m["depth_map_clamped"]),
                               current_stream()), "gps_raycast_to_maps");
-    if (ev_out) {
-        if (rc_event_next_ == rc_events_.size()) {
-            hipEvent_t ev;
-            hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-            rc_events_.push_back(ev);
-        }
-        *ev_out = rc_events_[rc_event_next_++];
-        hip_ok(hipEventRecord((hipEvent_t)*ev_out, c10::hip::getCurrentHIPStream().stream()), "hipEventRecord");
-    }
     stats.raycasts++;
     return m;
 }
 
+SLAMPipeline::RaycastStream& SLAMPipeline::raycastStream() {
+    if (!rc_) rc_.reset(new RaycastStream(raycast_stream_kind));
+    return *rc_;
+}
+
 void SLAMPipeline::beginAsyncRaycasts() {
-    window_raycast_events_.clear(); opt_raycast_events_.clear();
-    rc_event_next_ = 0;
+    if (rc_) rc_->next = 0;
     if (!async_raycasts) return;
-    if (!rc_stream_) {
-        rc_stream_ = new MapStream{make_stream(raycast_stream_kind)};
-        hipEvent_t ev;
-        hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-        ev_rc_begin_ = ev;
-    }
+    RaycastStream& rc = raycastStream();
     // the raycast stream starts behind everything the current stream holds (the fusion of the keyframe; the previous
     // update's last readers of the engine's free-view scratch)
-    hip_ok(hipEventRecord((hipEvent_t)ev_rc_begin_, c10::hip::getCurrentHIPStream().stream()), "hipEventRecord");
-    hip_ok(hipStreamWaitEvent(static_cast<MapStream*>(rc_stream_)->s.stream(), (hipEvent_t)ev_rc_begin_, 0), "hipStreamWaitEvent");
+    hip_ok(hipEventRecord(rc.begin, c10::hip::getCurrentHIPStream().stream()), "hipEventRecord");
+    hip_ok(hipStreamWaitEvent(rc.s.stream(), rc.begin, 0), "hipStreamWaitEvent");
 }
 
-void SLAMPipeline::waitRaycast(void* ev) {
-    if (ev) hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), (hipEvent_t)ev, 0), "hipStreamWaitEvent");
-}
-
-void SLAMPipeline::waitAllRaycasts() {
-    if (last_raycast_event_) { waitRaycast(last_raycast_event_); return; }   // (an adopted job's views: its last batch)
-    if (rc_event_next_ > 0) waitRaycast(rc_events_[rc_event_next_ - 1]);  // one stream: the last event covers all
-}
-
-// localFrameRaycast + keyFrameRaycast of the keyframe just fused, by the frame thread, into a job the map worker adopts later
-// (pipeline_raycasts): the same two batches, the same draws, the same tensors as raycastWindow + raycastKeyframes.
-void SLAMPipeline::buildUpdateViews(MapJob& out) {
-    const std::vector<ORUtils::SE3Pose>& poses = main_engine->camPoses;
-    void** evs = job_events_[job_parity_];
-    job_parity_ ^= 1;
-    std::vector<const Camera*> cams;
-    for (const Camera& cam : localframe_cam_window) cams.push_back(&cam);
-    void* ev = nullptr;
-    const double t0 = now_ms();
-    for (TensorDict& m : raycastCams(cams, poses, &ev, evs[0])) { out.window_raycasts.push_back(m); out.window_events.push_back(evs[0]); }
-    const double t1 = now_ms();
-    times.localFrameRaycast += t1 - t0;
-    out.opt_cams.assign(localframe_cam_window.begin(), localframe_cam_window.end());
-    out.window_len = localframe_cam_window.size();
-    out.opt_raycasts.assign(out.window_raycasts.begin(), out.window_raycasts.end());
-    out.opt_events = out.window_events;
-    out.last_event = cams.empty() ? nullptr : evs[0];
-    const int n = sample_method == "random" ? std::min<int>(keyframe_select_max, (int)keyframe_cam_list.size()) : 0;   // :538
-    if (n > 0) {
-        RandomSelector<Camera> sel(keyframe_cam_list, rng_kf_);
-        std::vector<const Camera*> kcams;
-        for (int k = 0; k < n; k++) {
-            const Camera* cam = sel.getNext().second;
-            out.opt_cams.push_back(*cam);
-            kcams.push_back(cam);
-        }
-        for (TensorDict& m : raycastCams(kcams, poses, &ev, evs[1])) { out.opt_raycasts.push_back(m); out.opt_events.push_back(evs[1]); }
-        out.last_event = evs[1];
-    }
-    times.keyFrameRaycast += now_ms() - t1;
-    out.views_ready = true;
+void SLAMPipeline::waitRaycast(RaycastEvent ev) {
+    if (ev) hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), ev, 0), "hipStreamWaitEvent");
 }
 
 // ------------------------------------------------------------------ frame bookkeeping (updateFrameList :319-360)
@@ -328,33 +319,32 @@ void SLAMPipeline::updateFrameList() {
     }
 }
 
-void SLAMPipeline::localFrameRaycast() { raycastWindow(localframe_cam_window, main_engine->camPoses); }
-void SLAMPipeline::keyFrameRaycast() { update_frame_id_ = curr_frame_id; raycastKeyframes(localframe_cam_window, keyframe_cam_list, main_engine->camPoses); }
+void SLAMPipeline::localFrameRaycast() { buildCurrentViews(liveSource(), kWindowBatch); }
+void SLAMPipeline::keyFrameRaycast() { buildCurrentViews(liveSource(), kKeyframeBatch); }
 void SLAMPipeline::initNewGaussians(TensorDict& rm) { initNewGaussiansFor(rm, curr_cam); }
 
 // runRaycastByCam for several cameras of ONE volume state: one batched free-view chain (TsdfEngine::runRaycastBatch) instead
 // of one chain per camera, then each view's tensor glue.  Same tensors as raycastCam per camera; one event covers them all.
 std::vector<TensorDict> SLAMPipeline::raycastCams(const std::vector<const Camera*>& cams,
-                                                  const std::vector<ORUtils::SE3Pose>& poses, void** ev_out, void* use_event) {
+                                                  const std::vector<ORUtils::SE3Pose>& poses, RaycastEvent* ev_out, RaycastEvent use_event) {
     std::vector<TensorDict> out;
     if (cams.empty()) return out;
+    requireEngine("raycast");
     TsdfEngine* eng = main_engine;
     const auto F = f32(device);
-    if (ev_out && !rc_stream_ && !use_event) beginAsyncRaycasts();  // (keyFrameRaycast() without a preceding localFrameRaycast())
     // Whose pool the result tensors come from.  They are WRITTEN on the raycast stream and READ on the consumer's (the stream
-    // current here: the map stream, or the frames stream in the sequential schedule).  Rounds 4-5 allocated them with the
-    // consumer's stream current -- fine while the worker enqueued the raycasts itself (the raycast stream was ordered behind
-    // the map stream), a write-after-read hazard once the FRAME thread enqueues update k+1's views while the worker is still
+    // current here: the map stream, or the frames stream in the sequential schedule).  Allocated with the consumer's stream
+    // current they would be a write-after-read hazard when the FRAME thread enqueues update k+1's views while the worker is still
     // running update k on the map stream: the caching allocator may hand out a block the worker freed a moment ago that queued
-    // map-stream kernels still read, and the raycast stream only waits for the frame's fusion (round-5 advisor finding).  Now:
-    // allocated with the RAYCAST stream current (a block of that pool is only reused in that stream's order) and the consumer
-    // registered with recordStream, so that a freed block waits for the consumer's queued work before the raycast stream gets
-    // it again; the consumer itself waits on the batch events as before.  (Only the allocations run under the raycast stream's
-    // guard: the pose glue below must not inherit it.)
+    // map-stream kernels still read, and the raycast stream only waits for the frame's fusion.  So: allocated with the RAYCAST
+    // stream current (a block of that pool is only reused in that stream's order) and the consumer registered with recordStream,
+    // so that a freed block waits for the consumer's queued work before the raycast stream gets it again; the consumer itself
+    // waits on the batch events.  (Only the allocations run under the raycast stream's guard: the pose glue below must not
+    // inherit it.)
     const c10::hip::HIPStream consumer = c10::hip::getCurrentHIPStream();
     auto result = [&](int64_t h, int64_t w, int64_t c) {
         c10::optional<c10::hip::HIPStreamGuard> alloc_on_rc;
-        if (ev_out) alloc_on_rc.emplace(static_cast<MapStream*>(rc_stream_)->s);
+        if (ev_out) alloc_on_rc.emplace(raycastStream().s);
         torch::Tensor t = torch::empty({h, w, c}, F);
         // (the allocator's own entry point: Tensor::record_stream wants a c10::Stream of the masquerading "cuda" device type)
         if (ev_out) c10::hip::HIPCachingAllocator::recordStream(t.storage().data_ptr(), consumer);
@@ -382,25 +372,13 @@ std::vector<TensorDict> SLAMPipeline::raycastCams(const std::vector<const Camera
     std::vector<torch::Tensor> w2c(cams.size());
     for (size_t k = 0; k < cams.size(); k++) {
         const Camera& cam = *cams[k];
-        if (cam.id >= 0 && cam.id < (int)poses.size()) {
-            view_poses[k] = poses[cam.id];
-        } else {
-            auto c = cam.c2w.to(torch::kCPU, torch::kFloat32).contiguous();
-            view_poses[k].SetInvM(c.data_ptr<float>());
-            view_poses[k].Coerce();
-        }
+        view_poses[k] = poseOf(cam, poses);
         view_intr[k] = intrinsicsOf(cam, eng);
-        TensorDict m;
-        m["color_map"] = result(cam.height, cam.width, 3);
-        m["vertex_map"] = result(cam.height, cam.width, 3);
-        m["confidence_map"] = result(cam.height, cam.width, 1);
-        m["depth_map"] = result(cam.height, cam.width, 1);
-        m["depth_map_clamped"] = result(cam.height, cam.width, 1);
-        out.push_back(m);
+        out.push_back(resultMaps(cam, result));
         w2c[k] = poseInv(cam.c2w.to(torch::kCPU, torch::kFloat32)).contiguous();  // poseInv(cam.c2w): dataset pose (:398)
     }
     c10::optional<c10::hip::HIPStreamGuard> on_rc;
-    if (ev_out) on_rc.emplace(static_cast<MapStream*>(rc_stream_)->s);
+    if (ev_out) on_rc.emplace(raycastStream().s);
     constexpr size_t kMaxBatch = 12;  // views per gps_tsdf_free_raycast_batch call; a later chunk reuses the render states in stream order
     for (size_t base = 0; base < cams.size(); base += kMaxBatch) {
         const size_t cnt = std::min(kMaxBatch, cams.size() - base);
@@ -415,91 +393,84 @@ std::vector<TensorDict> SLAMPipeline::raycastCams(const std::vector<const Camera
         eng->runRaycastBatch(std::vector<ORUtils::SE3Pose>(view_poses.begin() + base, view_poses.begin() + base + cnt), nullptr, &maps, &intr);
     }
     if (ev_out) {
-        if (use_event) {
-            *ev_out = use_event;
-        } else {
-            if (rc_event_next_ == rc_events_.size()) {
-                hipEvent_t ev;
-                hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-                rc_events_.push_back(ev);
-            }
-            *ev_out = rc_events_[rc_event_next_++];
-        }
-        hip_ok(hipEventRecord((hipEvent_t)*ev_out, c10::hip::getCurrentHIPStream().stream()), "hipEventRecord");
+        *ev_out = use_event ? use_event : raycastStream().nextEvent();
+        hip_ok(hipEventRecord(*ev_out, c10::hip::getCurrentHIPStream().stream()), "hipEventRecord");
     }
     stats.raycasts += (int64_t)cams.size();
     return out;
 }
 
-void SLAMPipeline::raycastWindow(const std::deque<Camera>& window, const std::vector<ORUtils::SE3Pose>& poses) {
-    localframe_raycast_window.clear();
-    beginAsyncRaycasts();
-    std::vector<const Camera*> cams;
-    for (const Camera& cam : window) cams.push_back(&cam);
-    void* ev = nullptr;
-    for (TensorDict& m : raycastCams(cams, poses, async_raycasts ? &ev : nullptr)) {
-        localframe_raycast_window.push_back(m);
-        window_raycast_events_.push_back(ev);
+// The view set of one map update: the local window's cameras, then (sample_method "random") up to keyframe_select_max history
+// keyframes drawn without replacement, each with its free-view raycast -- localFrameRaycast + keyFrameRaycast (:417-448, :528-561).
+// Every schedule builds its sets HERE, and the schedules give the same bits (test_overlapped_mapping_equals_sequential_schedule)
+// because of one rule: ONE draw loop per update, from rng_kf_ and nothing else, whichever thread builds the set and however the
+// views are batched.  rng_kf_ has no other user; the builds of successive updates never overlap (one frame thread, or one worker
+// the frame thread waits for), so every schedule draws the same numbers in the same order.
+SLAMPipeline::RaycastMs SLAMPipeline::buildViews(UpdateViews& out, const ViewSource& src, int parts, const RaycastEvent* job_events) {
+    requireEngine("raycast");
+    const bool one_batch = parts == kOneBatch, with_events = job_events || async_raycasts;
+    std::vector<const Camera*> cams;   // the batch being collected
+    auto raycastBatch = [&](RaycastEvent job_event) {
+        RaycastEvent ev = nullptr;
+        for (TensorDict& m : raycastCams(cams, src.poses, with_events ? &ev : nullptr, job_event)) {
+            out.raycasts.push_back(std::move(m));
+            out.events.push_back(ev);
+        }
+        if (ev) out.last_event = ev;
+        cams.clear();
+    };
+    // (the set `out` held before is released between the two batches -- after the single one -- and not earlier: the keyframes'
+    // batch then finds its blocks in the caching allocator again, and the steady-state footprint stays the warmed pool's)
+    UpdateViews previous;
+    const double t0 = now_ms();
+    if (parts & kWindowBatch) {
+        previous = std::move(out);
+        out = UpdateViews();
+        if (!job_events) beginAsyncRaycasts();   // (a job's raycast stream is ordered by the frame thread: keyframeStepThreaded)
+        out.cams.assign(src.window.begin(), src.window.end());
+        out.window_len = src.window.size();
+        for (const Camera& cam : src.window) cams.push_back(&cam);
+        if (!one_batch) raycastBatch(job_events ? job_events[0] : nullptr);
     }
+    const double t1 = now_ms();
+    if (parts & kKeyframeBatch) {
+        if (!one_batch) previous = UpdateViews();
+        if (parts == kKeyframeBatch) {   // the public two-step API: the window's views stay, history views of an earlier call go
+            out.cams.erase(out.cams.begin() + out.window_len, out.cams.end());
+            out.raycasts.erase(out.raycasts.begin() + out.window_len, out.raycasts.end());
+            out.events.resize(out.window_len);
+            if (async_raycasts && !rc_) beginAsyncRaycasts();   // (no localFrameRaycast() before it: order the raycast stream now)
+        }
+        out.frame_id = src.frame_id;
+        const int n = sample_method == "random" ? std::min<int>(keyframe_select_max, (int)src.keyframes.size()) : 0;   // :538
+        RandomSelector<Camera> sel(src.keyframes, rng_kf_);
+        for (int k = 0; k < n; k++) {
+            const Camera* cam = sel.getNext().second;
+            out.cams.push_back(*cam);
+            cams.push_back(cam);
+        }
+        raycastBatch(job_events ? job_events[1] : nullptr);
+    }
+    const double t2 = now_ms();
+    return one_batch ? RaycastMs{t2 - t0, 0.0} : RaycastMs{t1 - t0, t2 - t1};
 }
 
-void SLAMPipeline::raycastKeyframes(const std::deque<Camera>& window, const std::vector<Camera>& keyframes,
-                                    const std::vector<ORUtils::SE3Pose>& poses) {
-    opt_cam_list.assign(window.begin(), window.end());
-    opt_window_len_ = window.size(); opt_frame_id_ = update_frame_id_;   // (what checkKeyFrameError indexes / stamps with)
-    opt_raycast_list.assign(localframe_raycast_window.begin(), localframe_raycast_window.end());
-    opt_raycast_events_ = window_raycast_events_;
-    const int n = sample_method == "random" ? std::min<int>(keyframe_select_max, (int)keyframes.size()) : 0;   // :538
-    if (n == 0) return;
-    RandomSelector<Camera> sel(keyframes, rng_kf_);
-    std::vector<const Camera*> cams;
-    for (int k = 0; k < n; k++) {
-        const Camera* cam = sel.getNext().second;
-        opt_cam_list.push_back(*cam);
-        cams.push_back(cam);
-    }
-    void* ev = nullptr;
-    for (TensorDict& m : raycastCams(cams, poses, async_raycasts ? &ev : nullptr)) {
-        opt_raycast_list.push_back(m);
-        opt_raycast_events_.push_back(ev);
-    }
+SLAMPipeline::RaycastMs SLAMPipeline::buildCurrentViews(const ViewSource& src, int parts) {
+    if (parts & kWindowBatch) localframe_raycast_window.clear();   // (views_ alone holds the previous window's tensors: see buildViews)
+    const RaycastMs ms = buildViews(views_, src, parts);
+    if (parts & kWindowBatch) localframe_raycast_window.assign(views_.raycasts.begin(), views_.raycasts.begin() + views_.window_len);
+    return ms;
 }
 
-// localFrameRaycast + keyFrameRaycast of one keyframe update as ONE batch (what the keyframe-step functions call): same lists,
-// same random draws, same tensors; the window's and the keyframes' views share the launches.
-void SLAMPipeline::raycastWindowAndKeyframes(const std::deque<Camera>& window, const std::vector<Camera>& keyframes,
-                                             const std::vector<ORUtils::SE3Pose>& poses) {
-    localframe_raycast_window.clear();
-    beginAsyncRaycasts();
-    std::vector<const Camera*> cams;
-    for (const Camera& cam : window) cams.push_back(&cam);
-    opt_cam_list.assign(window.begin(), window.end());
-    opt_window_len_ = window.size(); opt_frame_id_ = update_frame_id_;   // (what checkKeyFrameError indexes / stamps with)
-    const int n = sample_method == "random" ? std::min<int>(keyframe_select_max, (int)keyframes.size()) : 0;   // :538
-    RandomSelector<Camera> sel(keyframes, rng_kf_);
-    for (int k = 0; k < n; k++) {
-        const Camera* cam = sel.getNext().second;
-        opt_cam_list.push_back(*cam);
-        cams.push_back(cam);
-    }
-    void* ev = nullptr;
-    std::vector<TensorDict> res = raycastCams(cams, poses, async_raycasts ? &ev : nullptr);
-    for (size_t k = 0; k < window.size(); k++) {
-        localframe_raycast_window.push_back(res[k]);
-        window_raycast_events_.push_back(ev);
-    }
-    opt_raycast_list.assign(localframe_raycast_window.begin(), localframe_raycast_window.end());
-    opt_raycast_events_ = window_raycast_events_;
-    for (size_t k = window.size(); k < res.size(); k++) {
-        opt_raycast_list.push_back(res[k]);
-        opt_raycast_events_.push_back(ev);
-    }
+void SLAMPipeline::adoptViews(UpdateViews&& v) {
+    views_ = std::move(v);
+    localframe_raycast_window.assign(views_.raycasts.begin(), views_.raycasts.begin() + views_.window_len);
 }
 
 // ------------------------------------------------------------------ initNewGaussians :450-526
 void SLAMPipeline::initNewGaussiansFor(TensorDict& rm, const Camera& cam) {
     torch::NoGradGuard no_grad;
-    if (!window_raycast_events_.empty()) waitRaycast(window_raycast_events_.back());  // rm is the newest window camera's result
+    if (views_.window_len > 0) waitRaycast(views_.eventOf(views_.window_len - 1));  // rm is the newest window camera's result
     const auto &depth = rm.at("depth_map"), &color = rm.at("color_map"), &vertex = rm.at("vertex_map");
     int frame_num = local_opt_interval;
     // valid = depth in (min, max) & vertex.sum(2) != 0;  mask = mean|src - image| > thres & valid [& alpha < max]: one launch
@@ -528,13 +499,13 @@ void SLAMPipeline::checkKeyFrameError() {
     torch::NoGradGuard no_grad;
     Config wc;
     wc.num["ssim_weight"] = ssim_weight; wc.num["depth_weight"] = depth_weight;
-    // The window length and frame number are those of the update the lists belong to (recorded when the lists were built): with
+    // The window length and frame number are those of the update the view set belongs to (recorded when it was built): with
     // overlapped / threaded mapping this check runs while the frame thread keeps pushing into localframe_cam_window and
     // advancing curr_frame_id, or one update late.  keyframe_loss_dict is shared with updateFrameList (frame thread): loss_mu_.
-    for (size_t k = opt_window_len_; k < opt_cam_list.size(); k++) {
-        const Camera& cam = opt_cam_list[k];
-        TensorDict& rc = opt_raycast_list[k];
-        if (k < opt_raycast_events_.size()) waitRaycast(opt_raycast_events_[k]);
+    for (size_t k = views_.window_len; k < views_.cams.size(); k++) {
+        const Camera& cam = views_.cams[k];
+        TensorDict& rc = views_.raycasts[k];
+        waitRaycast(views_.eventOf(k));
         auto res = model->forward(cam, rc.at("depth_map"), rc.at("color_map"));
         auto loss = model->computeLoss(res, cam, wc, rc.at("depth_map") > 0);
         const float total = loss.at("total").item<float>();
@@ -543,7 +514,7 @@ void SLAMPipeline::checkKeyFrameError() {
         auto it = keyframe_loss_dict.find(cam.id);
         float opt_count = it != keyframe_loss_dict.end() && it->second.size() > 3 ? it->second[3] : 0.f;
         if (total > loss_thres) opt_count += 1.f;
-        keyframe_loss_dict[cam.id] = {total, (float)opt_frame_id_, confidence_mean, opt_count};
+        keyframe_loss_dict[cam.id] = {total, (float)views_.frame_id, confidence_mean, opt_count};
     }
 }
 
@@ -557,7 +528,7 @@ void SLAMPipeline::localOptimizeBegin() {
     opt_pending_ = 0;
     if (model->getGaussianNum() == 0) return;
     model->initOptimizers(-1, scene_scale);
-    opt_loader_.reset(new RandomSelector<Camera>(opt_cam_list, rng_));
+    opt_loader_.reset(new RandomSelector<Camera>(views_.cams, rng_));
     opt_peek_valid_ = false;
     opt_pending_ = local_opt_iters;
 }
@@ -570,8 +541,8 @@ void SLAMPipeline::optimizeIterations(int count) {
         auto pick = opt_peek_valid_ ? opt_peek_ : opt_loader_->getNext();
         opt_peek_valid_ = false;
         const Camera& cam = *pick.second;
-        TensorDict& rc = opt_raycast_list[pick.first];
-        if (pick.first < (int)opt_raycast_events_.size()) waitRaycast(opt_raycast_events_[pick.first]);
+        TensorDict& rc = views_.raycasts[pick.first];
+        waitRaycast(views_.eventOf(pick.first));
         const Camera* next_cam = nullptr;
         if (prefetch_next_preprocess && opt_pending_ > 1 && !(ssim_weight > 0 || depth_weight > 0)) {
             opt_peek_ = opt_loader_->getNext();
@@ -610,7 +581,7 @@ void SLAMPipeline::removeRedundantGs() {
     const int64_t kept = model->pruneKeep(keep);
     // the host is synchronised with the map stream right here: look at the capacity flags the kernels cannot raise as exceptions
     model->checkBinningCapacity();
-    main_engine->checkRenderingBlocks();
+    if (main_engine) main_engine->checkRenderingBlocks();
     stats.pruned += N - kept;
 }
 
@@ -657,12 +628,10 @@ std::vector<TensorDict> SLAMPipeline::renderEvalImgs(const std::vector<Camera>& 
 }
 
 // ------------------------------------------------------------------ one SLAM frame (body of SLAMTrainCams :69-132)
-static std::atomic<double> g_job_post_ms{0.0};  // (debug aid only: when the frame thread woke the mapping thread)
-
 void SLAMPipeline::processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16) {
     curr_frame_id = i;
     const double tt0 = now_ms();
-    g_gate_wait_ms = g_handover_wait_ms = 0.0;
+    gate_wait_ms_ = handover_wait_ms_ = 0.0;
     if (!main_engine->trackingActive && (int)main_engine->gtC2wPoses.size() <= main_engine->framesProcessed)
         main_engine->gtC2wPoses.push_back(cam.c2w);
     ITMTrackingState* ts;
@@ -720,12 +689,13 @@ void SLAMPipeline::processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb
     const double thr = frame_report_ms, tt3 = now_ms();
     if (thr >= 0.0 && tt3 - tt0 > thr)
         fprintf(stderr, "[pipe] frame %d: %.3f ms = engine %.3f (tracker %.3f, fusion enqueue %.3f, gate wait %.3f) + toGPU %.3f + lists / keyframe step %.3f (hand-over wait %.3f)\n",
-                i, tt3 - tt0, tt1 - tt0, main_engine->trackDiag(14), main_engine->trackDiag(15), g_gate_wait_ms, tt2 - tt1, tt3 - tt2, g_handover_wait_ms);
+                i, tt3 - tt0, tt1 - tt0, main_engine->trackDiag(14), main_engine->trackDiag(15), gate_wait_ms_, tt2 - tt1, tt3 - tt2, handover_wait_ms_);
 }
 
 // ------------------------------------------------------------------ tracking / mapping overlap (see slam_pipeline.hpp)
 
 void SLAMPipeline::processFrame(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16) {
+    requireEngine("processFrame");
     // room for the tracker's evaluations beside the strip backward only while the two chains really run side by side (the strip
     // kernel alone is faster without the reserve: include/gps_slam_hip.h)
     gps_set_frame_chain_reserve(overlap_mapping ? frame_chain_reserve : 0);
@@ -735,10 +705,10 @@ void SLAMPipeline::processFrame(int i, Camera& cam, const torch::Tensor& rgb_u8,
     // caller's stream is re-joined in flush()
     ensureStreams();
     const hipStream_t caller = c10::hip::getCurrentHIPStream().stream();
-    c10::hip::HIPStream& fs = static_cast<MapStream*>(frame_stream_)->s;
+    c10::hip::HIPStream& fs = streams_->frame;
     if (caller != fs.stream()) {
-        hip_ok(hipEventRecord((hipEvent_t)ev_caller_, caller), "hipEventRecord");
-        hip_ok(hipStreamWaitEvent(fs.stream(), (hipEvent_t)ev_caller_, 0), "hipStreamWaitEvent");
+        hip_ok(hipEventRecord(streams_->caller, caller), "hipEventRecord");
+        hip_ok(hipStreamWaitEvent(fs.stream(), streams_->caller, 0), "hipStreamWaitEvent");
     }
     rethrowWorkerError();
     pumpMapping(pump_iters_per_frame);  // keep the map stream fed before this thread starts spinning on the tracker
@@ -747,58 +717,66 @@ void SLAMPipeline::processFrame(int i, Camera& cam, const torch::Tensor& rgb_u8,
 }
 
 void SLAMPipeline::ensureStreams() {
-    if (map_stream_) return;
-    map_stream_ = new MapStream{make_stream(map_stream_kind)};
-    frame_stream_ = new MapStream{make_stream(frame_stream_kind)};
-    for (void** e : {&ev_frame_, &ev_raycasts_, &ev_map_, &ev_caller_, &job_events_[0][0], &job_events_[0][1], &job_events_[1][0], &job_events_[1][1]}) {
-        hipEvent_t ev;
-        hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-        *e = ev;
-    }
+    if (!streams_) streams_.reset(new Streams(map_stream_kind, frame_stream_kind));
+}
+
+// ------------------------------------------------------------------ one map update (SLAMTrainCams :116-135)
+double SLAMPipeline::beginUpdate(const Camera& cam) {
+    initNewGaussiansFor(localframe_raycast_window.back(), cam);
+    const double t = now_ms();
+    localOptimizeBegin();
+    return t;
+}
+
+void SLAMPipeline::finishUpdate() {
+    removeRedundantGs();
+    if (sample_method == "ours") checkKeyFrameError();   // slam_pipeline.cpp:130-131
+}
+
+// The stages behind the raycasts, start to finish on the current stream, with the reference's stage timers (host time on the
+// calling thread: the map worker's are read by the frame thread only after flush()).
+void SLAMPipeline::runUpdate(const Camera& cam) {
+    const double s0 = now_ms();
+    const double s1 = beginUpdate(cam);
+    optimizeIterations(opt_pending_);
+    const double s2 = now_ms();
+    removeRedundantGs();
+    const double s3 = now_ms();
+    if (sample_method == "ours") checkKeyFrameError();   // slam_pipeline.cpp:130-131
+    waitAllRaycasts();  // the next frame's fusion modifies the volume (results no iteration drew would still be in flight)
+    times.initNewGaussians += s1 - s0; times.localOptimize += s2 - s1; times.removeGaussian += s3 - s2; times.checkError += now_ms() - s3;
 }
 
 void SLAMPipeline::keyframeStep() {
     // two batches: initNewGaussians only needs the window's views and starts while the keyframes' views render
-    const double t0 = now_ms();
-    localFrameRaycast();
-    const double t1 = now_ms();
-    keyFrameRaycast();
-    const double t2 = now_ms();
-    initNewGaussians(localframe_raycast_window.back());
-    const double t3 = now_ms();
-    localOptimize();
-    const double t4 = now_ms();
-    removeRedundantGs();
-    const double t5 = now_ms();
-    if (sample_method == "ours") checkKeyFrameError();   // slam_pipeline.cpp:130-131
-    waitAllRaycasts();  // the next frame's fusion modifies the volume (results no iteration drew would still be in flight)
-    times.localFrameRaycast += t1 - t0; times.keyFrameRaycast += t2 - t1; times.initNewGaussians += t3 - t2;
-    times.localOptimize += t4 - t3; times.removeGaussian += t5 - t4; times.checkError += now_ms() - t5;
+    bookRaycastMs(buildCurrentViews(liveSource(), kTwoBatches));
+    runUpdate(curr_cam);
+}
+
+// ------------------------------------------------------------------ tracking / mapping overlap (see slam_pipeline.hpp)
+void SLAMPipeline::finishDeferredUpdate() {
+    if (!prune_pending_) return;
+    c10::hip::HIPStreamGuard guard(streams_->map);
+    finishUpdate();
+    prune_pending_ = false;
 }
 
 void SLAMPipeline::keyframeStepOverlapped() {
     ensureStreams();
     const hipStream_t frames = c10::hip::getCurrentHIPStream().stream();
-    c10::hip::HIPStream& ms = static_cast<MapStream*>(map_stream_)->s;
-    // the previous update must be complete before its camera / raycast lists are replaced (host wait: B is idle afterwards)
+    c10::hip::HIPStream& ms = streams_->map;
+    // the previous update must be complete before its view set is replaced (host wait: B is idle afterwards)
     pumpMapping(opt_pending_);
-    if (map_in_flight_) { hip_ok(hipEventSynchronize((hipEvent_t)ev_map_), "hipEventSynchronize"); map_in_flight_ = false; }
-    hip_ok(hipEventRecord((hipEvent_t)ev_frame_, frames), "hipEventRecord");
-    hip_ok(hipStreamWaitEvent(ms.stream(), (hipEvent_t)ev_frame_, 0), "hipStreamWaitEvent");  // raycasts see frame i's volume
+    if (map_in_flight_) { hip_ok(hipEventSynchronize(streams_->map_done), "hipEventSynchronize"); map_in_flight_ = false; }
+    hip_ok(hipEventRecord(streams_->frame_fused, frames), "hipEventRecord");
+    hip_ok(hipStreamWaitEvent(ms.stream(), streams_->frame_fused, 0), "hipStreamWaitEvent");  // raycasts see frame i's volume
     {
         c10::hip::HIPStreamGuard guard(ms);
-        if (prune_pending_) {   // update k's prune (and loss records), before update k+1 reads the model and replaces the lists
-            removeRedundantGs();
-            if (sample_method == "ours") checkKeyFrameError();
-            prune_pending_ = false;
-        }
-        update_frame_id_ = curr_frame_id;
-        if (merge_keyframe_raycasts) raycastWindowAndKeyframes(localframe_cam_window, keyframe_cam_list, main_engine->camPoses);
-        else { localFrameRaycast(); keyFrameRaycast(); }
+        finishDeferredUpdate();   // update k's prune (and loss records), before update k+1 reads the model and replaces the views
+        buildCurrentViews(liveSource(), merge_keyframe_raycasts ? kOneBatch : kTwoBatches);
         if (async_raycasts) waitAllRaycasts();  // (this arrangement keeps its single map stream: the gate below covers them)
-        hip_ok(hipEventRecord((hipEvent_t)ev_raycasts_, ms.stream()), "hipEventRecord");
-        initNewGaussians(localframe_raycast_window.back());
-        localOptimizeBegin();
+        hip_ok(hipEventRecord(streams_->raycasts, ms.stream()), "hipEventRecord");
+        beginUpdate(curr_cam);
         map_update_open_ = true;
     }
     // a few iterations now, the rest a few at a time from the following processFrame calls: enqueueing all 20 at once keeps the
@@ -806,9 +784,8 @@ void SLAMPipeline::keyframeStepOverlapped() {
     pumpMapping(pump_iters_first);
     // the next frame's fusion must not modify the volume (or reuse the engine's free-view scratch) before the raycasts read it;
     // its tracking may overlap them: the wait sits in the engine's before-fusion hook
-    (void)frames;
     main_engine->beforeNextFusion = [this] {
-        hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), (hipEvent_t)ev_raycasts_, 0), "hipStreamWaitEvent");
+        hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), streams_->raycasts, 0), "hipStreamWaitEvent");
     };
 }
 
@@ -817,83 +794,86 @@ void SLAMPipeline::keyframeStepOverlapped() {
 // keyframe's map update start to finish on the map stream -- its host-side waits (mask counts in addGaussians / prune, 240
 // kernel launches) no longer stall the frame stream at all.  Hand-over at keyframe i: wait for update i-10, record "frame i
 // fused", snapshot the camera lists / poses the update reads (the frame thread keeps appending to the originals), wake the
-// worker, wait (~0.3 ms) until it has enqueued the raycasts and recorded their event, make the frame stream wait for it.
+// worker; the next frame's fusion waits until the update's raycasts have read the volume.
+void SLAMPipeline::waitWorkerIdle(std::unique_lock<std::mutex>& lk) {
+    cv_.wait(lk, [&] { return done_seq_ == job_seq_ || worker_error_; });
+}
+
+template <class Fill>
+void SLAMPipeline::postJob(Fill&& fill) {
+    std::unique_lock<std::mutex> lk(mu_);
+    if (!worker_.joinable()) worker_ = std::thread([this, dev = (int)c10::hip::current_device()] { mapWorker(dev); });
+    const double tw0 = now_ms();
+    waitWorkerIdle(lk);
+    handover_wait_ms_ = now_ms() - tw0;
+    if (worker_error_) { lk.unlock(); rethrowWorkerError(); }
+    fill(job_);   // (job_ is the frame thread's until job_seq_ moves)
+    job_seq_++;
+    job_post_ms_ = now_ms();
+    cv_.notify_all();
+}
+
 void SLAMPipeline::keyframeStepThreaded() {
     ensureStreams();
     const hipStream_t frames = c10::hip::getCurrentHIPStream().stream();
     if (pipeline_raycasts && async_raycasts) {
-        // (1) this keyframe's free views, now: the raycast stream starts behind frame i's fusion; the result tensors are allocated
-        // with the CONSUMER's stream current (the caching allocator ties a block to the stream it was allocated under)
-        if (!rc_stream_) {
-            rc_stream_ = new MapStream{make_stream(raycast_stream_kind)};
-            hipEvent_t ev;
-            hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-            ev_rc_begin_ = ev;
-        }
-        hip_ok(hipEventRecord((hipEvent_t)ev_frame_, frames), "hipEventRecord");
-        const hipStream_t rcs = static_cast<MapStream*>(rc_stream_)->s.stream();
-        hip_ok(hipStreamWaitEvent(rcs, (hipEvent_t)ev_frame_, 0), "hipStreamWaitEvent");
-        MapJob next;
-        next.curr_cam = curr_cam;
-        next.frame_id = curr_frame_id;
+        // This keyframe's free views, now, whether or not the worker has finished the previous update: the raycast stream starts
+        // behind frame i's fusion, the map stream is the results' consumer (raycastCams), the worker adopts the set when it gets here.
+        const hipStream_t rcs = raycastStream().s.stream();
+        hip_ok(hipEventRecord(streams_->frame_fused, frames), "hipEventRecord");
+        hip_ok(hipStreamWaitEvent(rcs, streams_->frame_fused, 0), "hipStreamWaitEvent");
+        UpdateViews views;
         {
-            c10::hip::HIPStreamGuard as_consumer(static_cast<MapStream*>(map_stream_)->s);
-            buildUpdateViews(next);
+            c10::hip::HIPStreamGuard as_consumer(streams_->map);
+            const Event* evs = streams_->job[job_parity_];
+            job_parity_ ^= 1;
+            const RaycastEvent job_events[2] = {evs[0], evs[1]};
+            bookRaycastMs(buildViews(views, liveSource(), kTwoBatches, job_events));
         }
-        hip_ok(hipEventRecord((hipEvent_t)ev_raycasts_, rcs), "hipEventRecord");
-        // (2) the next frame's fusion must not modify the volume before these raycasts have read it: a stream-side wait, no host wait
-        main_engine->beforeNextFusion = [this] {
-            hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), (hipEvent_t)ev_raycasts_, 0), "hipStreamWaitEvent");
-        };
-        // (3) hand the job over once the worker has finished the previous update
-        std::unique_lock<std::mutex> lk(mu_);
-        if (!worker_.joinable()) worker_ = std::thread([this, dev = (int)c10::hip::current_device()] { mapWorker(dev); });
-        const double tw0 = now_ms();
-        cv_.wait(lk, [&] { return done_seq_ == job_seq_ || worker_error_; });
-        g_handover_wait_ms = now_ms() - tw0;
-        if (worker_error_) { lk.unlock(); rethrowWorkerError(); }
-        job_ = std::move(next);
-        job_seq_++;
-        g_job_post_ms = now_ms();
-        cv_.notify_all();
-        return;
+        hip_ok(hipEventRecord(streams_->raycasts, rcs), "hipEventRecord");
+        postJob([&](MapJob& job) {
+            job.curr_cam = curr_cam;
+            job.views = std::move(views);
+            job.views_ready = true;
+        });
+    } else {
+        postJob([&](MapJob& job) {
+            hip_ok(hipEventRecord(streams_->frame_fused, frames), "hipEventRecord");
+            job.curr_cam = curr_cam;
+            job.views_ready = false;
+            job.window = localframe_cam_window;
+            job.keyframes = keyframe_cam_list;
+            job.poses = main_engine->camPoses;
+            job.frame_id = curr_frame_id;
+        });
     }
-    std::unique_lock<std::mutex> lk(mu_);
-    if (!worker_.joinable()) worker_ = std::thread([this, dev = (int)c10::hip::current_device()] { mapWorker(dev); });
-    const double tw0 = now_ms();
-    cv_.wait(lk, [&] { return done_seq_ == job_seq_ || worker_error_; });
-    g_handover_wait_ms = now_ms() - tw0;
-    if (worker_error_) { lk.unlock(); rethrowWorkerError(); }
-    hip_ok(hipEventRecord((hipEvent_t)ev_frame_, frames), "hipEventRecord");
-    job_.curr_cam = curr_cam;
-    job_.frame_id = curr_frame_id;
-    job_.window = localframe_cam_window;
-    job_.keyframes = keyframe_cam_list;
-    job_.poses = main_engine->camPoses;
-    job_seq_++;
-    g_job_post_ms = now_ms();
-    cv_.notify_all();
     // The next frame's fusion must not modify the volume (or reuse the engine's free-view scratch) before the update's raycasts
-    // have read it -- but its TRACKING may run meanwhile: the wait (for the worker to have recorded the event, then the
-    // stream-side wait on it) is deferred to the engine's before-fusion hook of the next ProcessFrame.
-    const int64_t want = job_seq_;
-    (void)frames;
-    main_engine->beforeNextFusion = [this, want] {
-        {
-            const double tw1 = now_ms();
-            std::unique_lock<std::mutex> lk2(mu_);
-            cv_.wait(lk2, [&] { return raycasts_seq_ >= want || worker_error_; });
-            g_gate_wait_ms = now_ms() - tw1;
-        }
-        rethrowWorkerError();
-        hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), (hipEvent_t)ev_raycasts_, 0), "hipStreamWaitEvent");
-    };
+    // have read it -- but its TRACKING may run meanwhile: the wait is deferred to the engine's before-fusion hook of the next
+    // ProcessFrame.  Two gates:
+    if (pipeline_raycasts && async_raycasts) {
+        // the raycasts are enqueued and their event recorded (above): a stream-side wait, no host wait
+        main_engine->beforeNextFusion = [this] {
+            hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), streams_->raycasts, 0), "hipStreamWaitEvent");
+        };
+    } else {
+        // the WORKER enqueues them: first a host wait for it to have recorded the event (raycasts_seq_), then the stream-side wait
+        main_engine->beforeNextFusion = [this, want = job_seq_] {
+            {
+                const double tw1 = now_ms();
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return raycasts_seq_ >= want || worker_error_; });
+                gate_wait_ms_ = now_ms() - tw1;
+            }
+            rethrowWorkerError();
+            hip_ok(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), streams_->raycasts, 0), "hipStreamWaitEvent");
+        };
+    }
 }
 
 void SLAMPipeline::mapWorker(int device_index) {
     try {
         c10::hip::set_device((c10::DeviceIndex)device_index);
-        c10::hip::HIPStream& ms = static_cast<MapStream*>(map_stream_)->s;
+        c10::hip::HIPStream& ms = streams_->map;
         c10::hip::HIPStreamGuard guard(ms);
         int64_t seen = 0;
         for (;;) {
@@ -905,54 +885,26 @@ void SLAMPipeline::mapWorker(int device_index) {
             }
             const double t_woke = now_ms();
             // job_ is stable until done_seq_ catches up (the frame thread waits for that before it writes the next one)
-            hip_ok(hipStreamWaitEvent(ms.stream(), (hipEvent_t)ev_frame_, 0), "hipStreamWaitEvent");  // raycasts see frame i's volume
-            update_frame_id_ = job_.frame_id;
+            hip_ok(hipStreamWaitEvent(ms.stream(), streams_->frame_fused, 0), "hipStreamWaitEvent");  // raycasts see frame i's volume
             if (job_.views_ready) {   // the frame thread has enqueued this update's views (and the gate event) already: adopt them
-                localframe_raycast_window = std::move(job_.window_raycasts);
-                window_raycast_events_ = std::move(job_.window_events);
-                opt_cam_list = std::move(job_.opt_cams);
-                opt_raycast_list = std::move(job_.opt_raycasts);
-                opt_raycast_events_ = std::move(job_.opt_events);
-                opt_window_len_ = job_.window_len; opt_frame_id_ = update_frame_id_;
-                last_raycast_event_ = job_.last_event;
-                { std::lock_guard<std::mutex> lk(mu_); raycasts_seq_ = seen; }
+                adoptViews(std::move(job_.views));
             } else {
-                last_raycast_event_ = nullptr;
-                const double r0 = now_ms();
-                if (merge_keyframe_raycasts) {
-                    raycastWindowAndKeyframes(job_.window, job_.keyframes, job_.poses);
-                    times.localFrameRaycast += now_ms() - r0;
-                } else {
-                    raycastWindow(job_.window, job_.poses);
-                    const double r1 = now_ms();
-                    raycastKeyframes(job_.window, job_.keyframes, job_.poses);
-                    times.localFrameRaycast += r1 - r0; times.keyFrameRaycast += now_ms() - r1;
-                }
+                const ViewSource snapshot{job_.window, job_.keyframes, job_.poses, job_.frame_id};
+                bookRaycastMs(buildCurrentViews(snapshot, merge_keyframe_raycasts ? kOneBatch : kTwoBatches));
                 // the gate of the next frame's fusion: the last raycast (on the raycast stream when they run beside the iterations)
-                hip_ok(hipEventRecord((hipEvent_t)ev_raycasts_, async_raycasts && rc_stream_ ? static_cast<MapStream*>(rc_stream_)->s.stream()
-                                                                                             : ms.stream()), "hipEventRecord");
-                { std::lock_guard<std::mutex> lk(mu_); raycasts_seq_ = seen; }
+                hip_ok(hipEventRecord(streams_->raycasts, async_raycasts && rc_ ? rc_->s.stream() : ms.stream()), "hipEventRecord");
             }
+            { std::lock_guard<std::mutex> lk(mu_); raycasts_seq_ = seen; }
             cv_.notify_all();
-            if (frame_report_ms >= 0.0 && now_ms() - g_job_post_ms > 1.0)
+            if (frame_report_ms >= 0.0 && now_ms() - job_post_ms_ > 1.0)
                 fprintf(stderr, "[pipe] update %lld: raycasts enqueued %.3f ms after the hand-over (woke after %.3f)\n", (long long)seen,
-                        now_ms() - g_job_post_ms, t_woke - g_job_post_ms);
-            // the stages' host time on THIS thread (the reference's stage timers, slam_pipeline.cpp:116-135, with the update moved
-            // here; read by the frame thread only after flush()); the wait for the map stream at the end is the iterations' GPU time
-            // the enqueues ran ahead of: booked under localOptimize, which it mostly is
+                        now_ms() - job_post_ms_, t_woke - job_post_ms_);
+            runUpdate(job_.curr_cam);
+            // the wait for the map stream is the iterations' GPU time the enqueues ran ahead of: booked under localOptimize, which it
+            // mostly is
             const double s0 = now_ms();
-            initNewGaussiansFor(localframe_raycast_window.back(), job_.curr_cam);
-            const double s1 = now_ms();
-            localOptimize();
-            const double s2 = now_ms();
-            removeRedundantGs();
-            const double s3 = now_ms();
-            if (sample_method == "ours") checkKeyFrameError();
-            const double s4 = now_ms();
-            waitAllRaycasts();
             hip_ok(hipStreamSynchronize(ms.stream()), "hipStreamSynchronize");
-            times.initNewGaussians += s1 - s0; times.localOptimize += (s2 - s1) + (now_ms() - s4); times.removeGaussian += s3 - s2;
-            times.checkError += s4 - s3;
+            times.localOptimize += now_ms() - s0;
             { std::lock_guard<std::mutex> lk(mu_); done_seq_ = seen; }
             cv_.notify_all();
         }
@@ -972,11 +924,11 @@ void SLAMPipeline::rethrowWorkerError() {
 // enqueue up to `count` pending optimise iterations on the map stream; closing the update records its completion event
 void SLAMPipeline::pumpMapping(int count) {
     if (!map_update_open_) return;
-    c10::hip::HIPStream& ms = static_cast<MapStream*>(map_stream_)->s;
+    c10::hip::HIPStream& ms = streams_->map;
     c10::hip::HIPStreamGuard guard(ms);
     optimizeIterations(count);
     if (opt_pending_ == 0) {
-        hip_ok(hipEventRecord((hipEvent_t)ev_map_, ms.stream()), "hipEventRecord");
+        hip_ok(hipEventRecord(streams_->map_done, ms.stream()), "hipEventRecord");
         map_update_open_ = false;
         map_in_flight_ = true;
         prune_pending_ = true;
@@ -984,22 +936,17 @@ void SLAMPipeline::pumpMapping(int count) {
 }
 
 void SLAMPipeline::flush() {
-    main_engine->beforeNextFusion = nullptr;  // no further frame: everything is joined below anyway
+    if (main_engine) main_engine->beforeNextFusion = nullptr;  // no further frame: everything is joined below anyway (no engine: detached)
     if (worker_.joinable()) {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return done_seq_ == job_seq_ || worker_error_; });
-        lk.unlock();
+        { std::unique_lock<std::mutex> lk(mu_); waitWorkerIdle(lk); }
         rethrowWorkerError();
     }
     pumpMapping(opt_pending_);
-    if (frame_stream_) hip_ok(hipStreamSynchronize(static_cast<MapStream*>(frame_stream_)->s.stream()), "hipStreamSynchronize");
-    if (map_in_flight_) { hip_ok(hipEventSynchronize((hipEvent_t)ev_map_), "hipEventSynchronize"); map_in_flight_ = false; }
+    if (streams_) hip_ok(hipStreamSynchronize(streams_->frame.stream()), "hipStreamSynchronize");
+    if (map_in_flight_) { hip_ok(hipEventSynchronize(streams_->map_done), "hipEventSynchronize"); map_in_flight_ = false; }
     if (prune_pending_) {
-        c10::hip::HIPStreamGuard guard(static_cast<MapStream*>(map_stream_)->s);
-        removeRedundantGs();
-        if (sample_method == "ours") checkKeyFrameError();
-        prune_pending_ = false;
-        hip_ok(hipStreamSynchronize(static_cast<MapStream*>(map_stream_)->s.stream()), "hipStreamSynchronize");
+        finishDeferredUpdate();
+        hip_ok(hipStreamSynchronize(streams_->map.stream()), "hipStreamSynchronize");
     }
 }
 
@@ -1013,21 +960,9 @@ SLAMPipeline::~SLAMPipeline() {
         cv_.notify_all();
         worker_.join();
     }
-    if (map_stream_) {
-        (void)hipStreamSynchronize(static_cast<MapStream*>(map_stream_)->s.stream());
-        (void)hipStreamSynchronize(static_cast<MapStream*>(frame_stream_)->s.stream());
-        for (void* e : {ev_frame_, ev_raycasts_, ev_map_, ev_caller_, job_events_[0][0], job_events_[0][1], job_events_[1][0], job_events_[1][1]}) if (e) (void)hipEventDestroy((hipEvent_t)e);
-        delete static_cast<MapStream*>(map_stream_);
-        delete static_cast<MapStream*>(frame_stream_);
-    }
-    // the free views' stream and its events (round 5: they used to outlive the pipeline -- one stream of the lowest-priority pool and
-    // a dozen events leaked per scene of a process that builds many)
-    if (rc_stream_) {
-        (void)hipStreamSynchronize(static_cast<MapStream*>(rc_stream_)->s.stream());
-        for (void* e : rc_events_) if (e) (void)hipEventDestroy((hipEvent_t)e);
-        if (ev_rc_begin_) (void)hipEventDestroy((hipEvent_t)ev_rc_begin_);
-        delete static_cast<MapStream*>(rc_stream_);
-    }
+    // (each synchronises its streams, then destroys its events; the streams themselves belong to the process: make_stream)
+    streams_.reset();
+    rc_.reset();
 }
 
 void SLAMPipeline::SLAMTrainCams(std::vector<Camera>& cams, const std::vector<torch::Tensor>& rgb_u8,

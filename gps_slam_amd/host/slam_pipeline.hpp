@@ -52,6 +52,9 @@ private:
 unsigned long long getGPUMemoryUsage(int gpu_id = 0);
 torch::Tensor computeNormalMap(const torch::Tensor& vertex_map);  // src/tensor_math.cpp:278-300 -> gps_normal_map
 
+struct ihipEvent_t;                     // (hipEvent_t's pointee: this header includes no HIP headers)
+using RaycastEvent = ihipEvent_t*;
+
 class SLAMPipeline {
 public:
     // use_gt_pose: TSDF.use_gt_pose of the configs (true in every shipped one) -> engine->turnOffTracking(), as
@@ -111,8 +114,6 @@ public:
     std::deque<Camera> localframe_cam_window;
     std::deque<TensorDict> localframe_raycast_window;
     std::vector<Camera> keyframe_cam_list;
-    std::vector<Camera> opt_cam_list;
-    std::vector<TensorDict> opt_raycast_list;
     float keyframe_theta_thres = 30.0f, keyframe_trans_thres = 0.3f;
     // keyframe_sample_configs (slam_pipeline.cpp:130, 293-317, 538): "random" draws keyframe_select_max history keyframes per update;
     // "ours" -- as the reference ships it -- adds NO history views (keyFrameRaycast has a "random" branch only) and keeps a loss
@@ -130,12 +131,13 @@ public:
     // LOG_PIPELINE_TIME of the reference (slam_pipeline.cpp:54-67, 73-96, 141-167): host wall-clock totals of one SLAMTrainCams run in
     // milliseconds.  `per_frame` is the reference's "per frame fusion time" (ProcessFrame + pose + toGPU + updateFrameList); FPS =
     // frames / (slam_total / 1000); run/read_results.py:38-39 derives Fusion-FPS = 1000 / per_frame and Gaussian-FPS =
-    // 1000 / (1000 / FPS - per_frame) from them.  The five per-stage totals are taken in the sequential keyframe step only (the
-    // overlapped schedules run the stages on another stream / thread; their host share of the frame thread is `keyframe_step`).
-    // slam_total here ends AFTER flush() and a device synchronise (the reference stops its clock with kernels still in flight).
-    // Under overlap_mapping / mapping_thread only per_frame (-> fusion_fps), slam_total (-> fps) and gpu_memory_mb mean what the
-    // reference's timers mean: localFrameRaycast / keyFrameRaycast are then the frame thread's ENQUEUE time, localOptimize includes
-    // the map stream's synchronisation wait -- not comparable with the reference's per-stage numbers (sequential schedule: they are).
+    // 1000 / (1000 / FPS - per_frame) from them.  slam_total here ends AFTER flush() and a device synchronise (the reference stops
+    // its clock with kernels still in flight).  The per-stage totals are HOST time of the thread that runs the stage, comparable with
+    // the reference's in the sequential schedule only.  Under overlap: streams-only books none of them (its host share of the frame
+    // thread is `keyframe_step`); with the mapping thread localFrameRaycast / keyFrameRaycast are the ENQUEUE time of whoever builds
+    // the views (frame thread with pipeline_raycasts, else the worker; one batch: all under localFrameRaycast), the other stages are
+    // the worker's, and localOptimize includes its wait for the map stream.  per_frame, slam_total and gpu_memory_mb always mean
+    // what the reference's mean.
     struct PipelineTimes {
         int frames = 0;
         double slam_total = 0, per_frame = 0, keyframe_step = 0, localFrameRaycast = 0, keyFrameRaycast = 0, initNewGaussians = 0,
@@ -210,42 +212,84 @@ public:
     std::vector<torch::Tensor> trace_live, trace_counters, trace_poses;
     ~SLAMPipeline();
 
+    // One map update's view set: the cameras it optimises over (the local window first, then the history keyframes), each camera's
+    // free-view raycast and the event behind that result (nullptr: the result is ordered by the stream itself).
+    struct UpdateViews {
+        std::vector<Camera> cams;
+        std::vector<TensorDict> raycasts;
+        std::vector<RaycastEvent> events;    // parallel to raycasts for the views the builder made; a view appended by hand has none
+        size_t window_len = 0;               // length of the local window at the front (what checkKeyFrameError skips)
+        int frame_id = 0;                    // frame number of the update the set belongs to (what checkKeyFrameError stamps with)
+        RaycastEvent last_event = nullptr;   // the last batch's: one raycast stream, so it covers every result of the set
+        RaycastEvent eventOf(size_t k) const { return k < events.size() ? events[k] : nullptr; }
+    };
+
 private:
-    void processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16);
+    UpdateViews views_;   // the current update's
+
+public:
+    // slam_pipeline.h names of the current set (the drop-in surface): the same storage
+    std::vector<Camera>& opt_cam_list = views_.cams;
+    std::vector<TensorDict>& opt_raycast_list = views_.raycasts;
+
+private:
+    struct Streams;         // map + frame stream and the fixed events between them (defined in the .cpp: no HIP / c10 stream headers here)
+    struct RaycastStream;   // the free views' stream, its "volume complete" event and the pooled per-batch events
+    std::unique_ptr<Streams> streams_;      // created by the first overlapped frame
+    std::unique_ptr<RaycastStream> rc_;     // created by the first asynchronous raycast
     void ensureStreams();
-    // `ev_out` != nullptr: run on the raycast stream and hand back the event that marks the result complete
-    TensorDict raycastCam(const Camera& cam, const std::vector<ORUtils::SE3Pose>& poses, void** ev_out = nullptr);
-    // the same for several cameras of one volume state in ONE batched free-view chain; one event for all results
-    // (use_event: record THIS event behind the batch instead of one of the update's pooled events)
+    RaycastStream& raycastStream();
+    void requireEngine(const char* who) const;   // TORCH_CHECK: an engine is attached (not shut down / detached)
+
+    void processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16);
+    // one camera's free view on the current stream, un-batched (runRaycastByCam, renderEvalImgs)
+    TensorDict raycastCam(const Camera& cam, const std::vector<ORUtils::SE3Pose>& poses);
+    // the same for several cameras of one volume state in ONE batched free-view chain.  ev_out != nullptr: on the raycast stream, and
+    // *ev_out is the one event behind all results (use_event: record THIS event instead of one of the update's pooled events)
     std::vector<TensorDict> raycastCams(const std::vector<const Camera*>& cams, const std::vector<ORUtils::SE3Pose>& poses,
-                                        void** ev_out = nullptr, void* use_event = nullptr);
-    void raycastWindowAndKeyframes(const std::deque<Camera>& window, const std::vector<Camera>& keyframes,
-                                   const std::vector<ORUtils::SE3Pose>& poses);
-    void raycastWindow(const std::deque<Camera>& window, const std::vector<ORUtils::SE3Pose>& poses);
-    void raycastKeyframes(const std::deque<Camera>& window, const std::vector<Camera>& keyframes,
-                          const std::vector<ORUtils::SE3Pose>& poses);
+                                        RaycastEvent* ev_out = nullptr, RaycastEvent use_event = nullptr);
+    // where a view set is built from: the live lists (sequential / streams-only schedule, the frame thread's enqueue) or a job's
+    // snapshot of them (the worker raycasts itself while the frame thread keeps appending to the originals)
+    struct ViewSource {
+        const std::deque<Camera>& window; const std::vector<Camera>& keyframes; const std::vector<ORUtils::SE3Pose>& poses; int frame_id;
+    };
+    ViewSource liveSource() const { return {localframe_cam_window, keyframe_cam_list, main_engine->camPoses, curr_frame_id}; }
+    enum ViewParts { kWindowBatch = 1, kKeyframeBatch = 2, kTwoBatches = 3, kOneBatch = 7 };   // kOneBatch: window + keyframes share the launches
+    struct RaycastMs { double window = 0, keyframes = 0; };   // host time of the two steps (one batch: all under `window`)
+    // THE builder of a view set (see the .cpp for the rule the schedules' bit-equality rests on).  job_events: the {window, keyframe}
+    // events of a job the frame thread enqueues; nullptr: pooled events (async_raycasts) or none
+    RaycastMs buildViews(UpdateViews& out, const ViewSource& src, int parts, const RaycastEvent* job_events = nullptr);
+    RaycastMs buildCurrentViews(const ViewSource& src, int parts);   // ... into views_ (+ localframe_raycast_window)
+    void adoptViews(UpdateViews&& v);
+    void bookRaycastMs(const RaycastMs& ms) { times.localFrameRaycast += ms.window; times.keyFrameRaycast += ms.keyframes; }
+
     void initNewGaussiansFor(TensorDict& raycast_maps, const Camera& cam);
+    // The pieces of one update.  runUpdate is the whole stage sequence with the stage timers (sequential schedule, map worker); the
+    // streams-only schedule opens an update with beginUpdate, pumps the iterations from later frames and defers finishUpdate.
+    double beginUpdate(const Camera& cam);   // initNewGaussians + localOptimizeBegin; returns the host time between the two
+    void finishUpdate();                     // prune + ("ours") loss records
+    void runUpdate(const Camera& cam);
+    void finishDeferredUpdate();             // streams-only: update k's finishUpdate, on the map stream, if it is still owed
     void keyframeStep();
     void keyframeStepOverlapped();
     void keyframeStepThreaded();
     void mapWorker(int device_index);
     void rethrowWorkerError();
     struct MapJob {
-        Camera curr_cam; int frame_id = 0; std::deque<Camera> window; std::vector<Camera> keyframes; std::vector<ORUtils::SE3Pose> poses;
+        Camera curr_cam;
         // pipeline_raycasts: the update's views, already enqueued by the frame thread (the worker adopts them instead of raycasting)
         bool views_ready = false;
-        std::vector<Camera> opt_cams; std::vector<TensorDict> opt_raycasts; std::vector<void*> opt_events;
-        std::deque<TensorDict> window_raycasts; std::vector<void*> window_events;
-        size_t window_len = 0; void* last_event = nullptr;
+        UpdateViews views;
+        // otherwise: what the worker builds them from
+        std::deque<Camera> window; std::vector<Camera> keyframes; std::vector<ORUtils::SE3Pose> poses; int frame_id = 0;
     };
     MapJob job_;
-    void buildUpdateViews(MapJob& out);           // localFrameRaycast + keyFrameRaycast of the keyframe at hand into `out` (frame thread)
-    void* job_events_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // {window batch, keyframe batch} per update parity
-    int job_parity_ = 0;
-    void* last_raycast_event_ = nullptr;          // the adopted job's last batch (waitAllRaycasts)
+    // The threaded hand-over: start the worker if needed, wait until the previous update is done or has failed, rethrow its error,
+    // let `fill` write job_, wake the worker.  waitWorkerIdle is the wait alone (flush()).
+    template <class Fill> void postJob(Fill&& fill);
+    void waitWorkerIdle(std::unique_lock<std::mutex>& lk);
+    int job_parity_ = 0;                          // which of Streams::job's two event pairs the next enqueued job gets
     std::mt19937_64 rng_kf_;                      // the history keyframes' draw (its own generator: the frame thread draws while the worker's update draws cameras)
-    size_t opt_window_len_ = 0;                  // length of the local window at the front of opt_cam_list (the rest: history keyframes)
-    int opt_frame_id_ = 0, update_frame_id_ = 0; // frame number of the update opt_cam_list belongs to / of the update being built
     std::mutex loss_mu_;                         // keyframe_loss_dict: written by updateFrameList (frame thread) and checkKeyFrameError (map thread)
     std::thread worker_;
     std::mutex mu_;
@@ -253,6 +297,10 @@ private:
     int64_t job_seq_ = 0, raycasts_seq_ = 0, done_seq_ = 0;
     bool stop_ = false;
     std::exception_ptr worker_error_;
+    // host time the frame thread spent WAITING for the map worker inside the last processFrame call: for the previous update to finish
+    // (hand-over at a keyframe) and for this update's raycasts to be enqueued (gate of the next frame's fusion)
+    double gate_wait_ms_ = 0.0, handover_wait_ms_ = 0.0;
+    std::atomic<double> job_post_ms_{0.0};        // (debug aid only: when the frame thread woke the mapping thread)
     void localOptimizeBegin();
     void optimizeIterations(int count);
     void pumpMapping(int count);
@@ -263,18 +311,11 @@ private:
     bool map_update_open_ = false;
     std::mt19937_64 rng_;
     at::Generator gen_;
-    void *map_stream_ = nullptr, *frame_stream_ = nullptr;  // c10 stream handle storage (see .cpp)
     // A keyframe's free-view raycasts on a stream of their own, next to the optimise iterations (they only read the volume; the
     // rasterizer kernels fill the GPU their latency-bound tails leave idle): every result carries an event, and whoever reads
     // a result (initNewGaussians, an optimise iteration) makes its stream wait for it.
-    void* rc_stream_ = nullptr;
-    void* ev_rc_begin_ = nullptr;                 // "the volume the raycasts read is complete" (recorded on the issuing stream)
-    std::vector<void*> rc_events_;                // hipEvent_t pool, one per raycast of the current update
-    size_t rc_event_next_ = 0;
-    std::vector<void*> window_raycast_events_, opt_raycast_events_;  // parallel to localframe_raycast_window / opt_raycast_list
     void beginAsyncRaycasts();                    // call once per update, on the stream that is ordered after the volume
-    void waitRaycast(void* ev);                   // current stream waits for one result (no-op for nullptr)
-    void waitAllRaycasts();                       // ... for all of this update's
-    void *ev_frame_ = nullptr, *ev_raycasts_ = nullptr, *ev_map_ = nullptr, *ev_caller_ = nullptr;  // hipEvent_t
+    void waitRaycast(RaycastEvent ev);            // current stream waits for one result (no-op for nullptr)
+    void waitAllRaycasts() { waitRaycast(views_.last_event); }   // ... for all of the current update's
     bool map_in_flight_ = false, prune_pending_ = false;
 };

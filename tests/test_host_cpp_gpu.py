@@ -646,7 +646,7 @@ def test_overlapped_mapping_equals_sequential_schedule():
     rgb = torch.as_tensor(rgba).to(DEV)
     dep = torch.as_tensor(seq["depth"].astype(np.int16)).to(DEV)
 
-    def run(overlap, thread=False, merge=False):
+    def run(overlap, thread=False, merge=False, pipeline_raycasts=True, async_raycasts=True):
         eng = h.ITMBasicEngine(W, Hh, seq["fx"], seq["fy"], seq["cx"], seq["cy"], 0.01, 0.04, 0.2, 10.0)
         model = h.SLAMGaussianModel()
         model.loadConfig(dict(capacity=1 << 16))
@@ -654,6 +654,8 @@ def test_overlapped_mapping_equals_sequential_schedule():
         pipe.overlap_mapping = overlap
         pipe.mapping_thread = thread
         pipe.merge_keyframe_raycasts = merge  # an update's free views as one batch instead of window + keyframes
+        pipe.pipeline_raycasts = pipeline_raycasts  # mapping thread: the frame thread enqueues the views (False: the worker itself)
+        pipe.async_raycasts = async_raycasts  # the free views on a stream of their own beside the iterations
         for i in range(n):
             c = h.Camera(W, Hh, seq["fx"], seq["fy"], seq["cx"], seq["cy"], True, torch.as_tensor(seq["c2w"][i].astype(np.float32)))
             c.id = i
@@ -676,8 +678,11 @@ def test_overlapped_mapping_equals_sequential_schedule():
     st_t2, _, _, par_t2 = run(True, True)
     assert st_t == st_t2 and all(torch.equal(a, b) for a, b in zip(par_t, par_t2)), "overlap schedule (mapping thread): two runs differ"
     assert all(torch.equal(a, b) for a, b in zip(par_s, par_t)), "overlap schedule != sequential schedule"
-    # streams on one host thread; tracking thread + mapping thread; the latter with one free-view batch per update
-    for mode in ((True, False), (True, True), (True, True, True)):
+    # streams on one host thread; tracking thread + mapping thread; the latter with one free-view batch per update; the mapping
+    # thread raycasting itself (the second hand-over, the worker's own view build); without the raycast stream; streams on one host
+    # thread with one free-view batch per update
+    for mode in ((True, False), (True, True), (True, True, True), (True, True, False, False), (True, True, False, True, False),
+                 (True, False, True)):
         st_o, cnt_o, live_o, par_o = run(*mode)
         assert st_s == st_o and st_s["opt_iters"] == 60 and st_s["added"] > 100
         assert torch.equal(cnt_s[:4], cnt_o[:4]) and torch.equal(live_s, live_o)

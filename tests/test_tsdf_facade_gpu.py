@@ -174,3 +174,44 @@ def test_pipeline_on_cli_engine_equals_pipeline_on_device_tensors():
     # est_pose went into cams[i].c2w_slam (slam_pipeline.cpp:81-83)
     assert torch.allclose(cams[5].c2w_slam.cpu(), torch.as_tensor(seq["c2w"][5].astype(np.float32)), atol=1e-5)
     cli.Shutdown()
+
+
+def test_pipeline_outlives_its_engine_and_takes_a_new_one():
+    """After CLIEngine::Shutdown() the pipeline holds no engine: the accessors that flush first still return, a further frame raises
+    instead of dereferencing the freed engine; and the pipeline takes a new engine afterwards.  (Host pointers only.)"""
+    h = _host()
+    W, H, n = 160, 120, 4
+    seq = synth.make_sequence(W, H, n, step_deg=0.5)
+    cfg = dict(voxel_size=0.01, trunc_dist=0.04, viewFrustum_min=0.2, viewFrustum_max=10.0, use_gt_pose=1)
+
+    def cam(i):
+        c = h.Camera(W, H, seq["fx"], seq["fy"], seq["cx"], seq["cy"], True, torch.as_tensor(seq["c2w"][i].astype(np.float32)))
+        c.id = i
+        return c
+
+    model = h.SLAMGaussianModel()
+    model.loadConfig(dict(capacity=1 << 12))
+    pipe = h.SLAMPipeline(7)
+    pipe.setModel(model)
+    cli = h.createTsdfEngine(_reader(h, seq, n)[0], cfg)
+    pipe.setTsdfEngine(cli)
+    for i in range(3):
+        pipe.processFrameCLI(i, cam(i))
+    cli.Shutdown()
+    assert pipe.stats()["frames"] == 3
+    assert pipe.keyframeCount() >= 1
+    assert pipe.optCams() == [] and pipe.optRaycasts() == []
+    assert isinstance(pipe.keyframeLossDict(), dict)
+    with pytest.raises(RuntimeError, match="shut down"):
+        pipe.processFrameCLI(3, cam(3))
+    # a second engine on the same pipeline.  (CLIEngine is the reference's process-wide singleton: createTsdfEngine hands out one
+    # object at a time, so "second" can only be made once "first" is gone -- two live ones exist for C++ callers alone.)
+    second = h.createTsdfEngine(_reader(h, seq, n)[0], cfg)
+    pipe.setTsdfEngine(second)
+    pipe.setTsdfEngine(second)   # attaching again lets go first: no hook of the earlier attachment survives
+    pipe.processFrameCLI(0, cam(0))
+    pipe.processFrameCLI(1, cam(1))
+    assert pipe.stats()["frames"] == 5 and second.currentFrameNo == 2
+    second.Shutdown()
+    with pytest.raises(RuntimeError, match="shut down"):
+        pipe.processFrameCLI(2, cam(2))
