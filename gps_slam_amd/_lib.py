@@ -57,6 +57,8 @@ class SplatStep(C.Structure):
                                                                    "sh_rest")] +
                 [("lr", f64 * 6), ("beta1", f64), ("beta2", f64), ("adam_eps", f64), ("fuse_sh_rest_adam", i32)] +
                 [(n, vp) for n in ("v_rows", "pix2", "cls_ids", "cls_counts")] + [("cls_stride", i64)] +
+                [("ssim_weight", f32), ("depth_weight", f32)] +
+                [(n, vp) for n in ("ref_depth_raw", "gt_depth", "depth", "loss_terms", "loss_ws")] +
                 [(n, vp) for n in ("next_viewmat", "next_Kmat", "next_cam_pos")] + [("preprocessed", i32)] +
                 [(n, vp) for n in ("exposure", "exposure_grad", "exposure_m", "exposure_v", "exposure_slab")] +
                 [(n, i32) for n in ("exposure_rows", "exposure_row", "exposure_step")] + [("exposure_lr", f64)])
@@ -99,6 +101,8 @@ PROTOTYPES = {
     "gps_raster_ges_bwd_exact": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
     "gps_compose_l1": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gps_adam_step": (i32, [C.POINTER(AdamSegment), i32, f64, f64, f64, i32, vp]),
+    "gps_loss_terms_workspace_floats": (i64, [i32, i32]),
+    "gps_loss_terms": (i32, [i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gps_exposure_slab_floats": (i64, [i32, i32]),
     "gps_compose_exposure": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gps_exposure_fwd": (i32, [i32, vp, vp, vp, vp]),

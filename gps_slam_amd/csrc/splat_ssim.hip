@@ -11,19 +11,11 @@
 // reference's `.permute().contiguous()` copies disappear.  Tap order and the use of fused multiply-adds follow the reference
 // (`val += G_k * p` contracted by nvcc).
 #include "common.hpp"
+#include "splat_ssim.hpp"
 
 namespace {
 
-constexpr int TS = 32;          // output tile edge
-constexpr int HALO = 5;
-constexpr int TIN = TS + 2 * HALO;  // 42
-constexpr int LD_IN = TIN + 1;      // padded row stride of the input tiles
-constexpr int LD_H = TS + 1;        // padded row stride of the x-pass results
-
-__device__ __constant__ float G[11] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f,
-                                       0.10936068743467331f,  0.21300552785396576f,   0.26601171493530273f,
-                                       0.21300552785396576f,  0.10936068743467331f,   0.036000773310661316f,
-                                       0.0075987582094967365f, 0.001028380123898387f};
+using namespace gps::ssim;   // the window, the tile geometry and the two passes (shared with splat_loss.hip)
 
 struct Layout { int64_t sb, sc, sy, sx; };  // element strides of (batch, channel, row, column)
 __host__ __device__ inline Layout make_layout(int CH, int H, int W, int channels_last) {
@@ -54,43 +46,22 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(int H, int W, int CH, flo
     __syncthreads();
     for (int q = tid; q < TIN * TS; q += 256) {  // x-pass: row ly of the halo tile, output column lx
         const int ly = q / TS, lx = q - ly * TS;
-        float s1 = 0.f, s11 = 0.f, s2 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float p = a[ly][lx + k], r = bb[ly][lx + k];
-            s1 = fmaf(G[k], p, s1);
-            s11 = fmaf(G[k], p * p, s11);
-            s2 = fmaf(G[k], r, s2);
-            s22 = fmaf(G[k], r * r, s22);
-            s12 = fmaf(G[k], p * r, s12);
-        }
-        h[0][ly][lx] = s1; h[1][ly][lx] = s11; h[2][ly][lx] = s2; h[3][ly][lx] = s22; h[4][ly][lx] = s12;
+        xpass5(a, bb, h, ly, lx);
     }
     __syncthreads();
     for (int q = tid; q < TS * TS; q += 256) {  // y-pass + the SSIM expression
         const int ly = q / TS, lx = q - ly * TS;
-        float mu1 = 0.f, e11 = 0.f, mu2 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            mu1 = fmaf(G[k], h[0][ly + k][lx], mu1);
-            e11 = fmaf(G[k], h[1][ly + k][lx], e11);
-            mu2 = fmaf(G[k], h[2][ly + k][lx], mu2);
-            e22 = fmaf(G[k], h[3][ly + k][lx], e22);
-            e12 = fmaf(G[k], h[4][ly + k][lx], e12);
-        }
+        float mu1, e11, mu2, e22, e12;
+        ypass5(h, ly, lx, mu1, e11, mu2, e22, e12);
         const int x = x0 + lx, y = y0 + ly;
         if (x >= W || y >= H) continue;
-        const float sigma1_sq = e11 - mu1 * mu1, sigma2_sq = e22 - mu2 * mu2, sigma12 = e12 - mu1 * mu2;
-        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
-        const float C = 2.0f * mu1_mu2 + C1, D = 2.0f * sigma12 + C2;
-        const float A = mu1_sq + mu2_sq + C1, B = sigma1_sq + sigma2_sq + C2;
+        const Point pt = point(mu1, e11, mu2, e22, e12, C1, C2);
         const int64_t o = b * l.sb + c * l.sc + y * l.sy + x * l.sx;
-        ssim_map[o] = (C * D) / (A * B);
+        ssim_map[o] = value(pt);
         if (dm_dmu1) {
-            dm_dmu1[o] = (mu2 * 2.0f * D) / (A * B) - (mu2 * 2.0f * C) / (A * B) - (mu1 * 2.0f * C * D) / (A * A * B) +
-                         (mu1 * 2.0f * C * D) / (A * B * B);
-            dm_dsigma1_sq[o] = (-C * D) / (A * B * B);
-            dm_dsigma12[o] = (2 * C) / (A * B);
+            dm_dmu1[o] = d_mu1(pt);
+            dm_dsigma1_sq[o] = d_sigma1_sq(pt);
+            dm_dsigma12[o] = d_sigma12(pt);
         }
     }
 }
@@ -115,34 +86,15 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(int H, int W, int CH, Lay
     __syncthreads();
     for (int q = tid; q < TIN * TS; q += 256) {
         const int ly = q / TS, lx = q - ly * TS;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            s0 = fmaf(G[k], t[0][ly][lx + k], s0);
-            s1 = fmaf(G[k], t[1][ly][lx + k], s1);
-            s2 = fmaf(G[k], t[2][ly][lx + k], s2);
-        }
-        h[0][ly][lx] = s0; h[1][ly][lx] = s1; h[2][ly][lx] = s2;
+        xpass3(t, h, ly, lx);
     }
     __syncthreads();
     for (int q = tid; q < TS * TS; q += 256) {
         const int ly = q / TS, lx = q - ly * TS;
         const int x = x0 + lx, y = y0 + ly;
         if (x >= W || y >= H) continue;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            v0 = fmaf(G[k], h[0][ly + k][lx], v0);
-            v1 = fmaf(G[k], h[1][ly + k][lx], v1);
-            v2 = fmaf(G[k], h[2][ly + k][lx], v2);
-        }
         const int64_t o = b * l.sb + c * l.sc + y * l.sy + x * l.sx;
-        const float p1 = img1[o], p2 = img2[o];
-        float d = 0.0f;
-        d += v0;
-        d += p1 * 2.0f * v1;
-        d += p2 * v2;
-        dL_dimg1[o] = d;
+        dL_dimg1[o] = ypass3(h, ly, lx, img1[o], img2[o]);
     }
 }
 

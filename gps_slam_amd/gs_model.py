@@ -465,14 +465,19 @@ class RawGaussianModel:
         N = self.getGaussianNum()
         return [t[:N] for t in self._opt["g"]]
 
-    def train_step(self, cam, ref_depth, base_color, gt_rgb, ref_depth_clamped=None, next_cam=None):
+    def train_step(self, cam, ref_depth, base_color, gt_rgb, ref_depth_clamped=None, next_cam=None, ssim_weight=0.0,
+                   depth_weight=0.0, gt_depth=None):
         """model.forward -> computeLoss -> loss.backward -> optimizersStep/ZeroGrad (slam_pipeline.cpp:247-254) as one
         C-ABI call (gps_splat_train_step).  The L1 loss accumulates in a device scalar (loss_sum()).
         next_cam: the camera of the NEXT train_step call (same size) -- its preprocessing forward then runs in the tail of this
         step's backward kernel (gps_splat_step::next_viewmat) and the next call skips its preprocessing launch, provided it is
         called with that camera and nothing else has used the model in between (any other call, an add / prune / load of the
         parameters: the forward run ahead is discarded and the step preprocesses again; editing the parameter tensors in place is
-        the one thing this cannot see); ignored where the step cannot prefetch."""
+        the one thing this cannot see); ignored where the step cannot prefetch.
+        ssim_weight / depth_weight (computeLoss's weights, raw_gs_model.cpp:369-417; gt_depth: the frame's depth [H,W,1] or None
+        for a camera without one): with a non-zero weight the step carries those loss terms as well (gps_splat_step::ssim_weight
+        ..); loss_sum() then HOLDS this step's total and loss_terms() = {total, L1 mean, 1 - mean SSIM, depth L1}.  Not together
+        with an exposure row of the camera (gps_splat_train_step refuses it)."""
         if ref_depth_clamped is None:
             ref_depth_clamped = self.clamp_ref_depth(ref_depth)
         st = self._step_struct(cam.width, cam.height)
@@ -500,9 +505,26 @@ class RawGaussianModel:
             st.exposure_m, st.exposure_v, st.exposure_slab = e["m"].data_ptr(), e["v"].data_ptr(), e["slab"].data_ptr()
             st.exposure_rows, st.exposure_row = self.opt_gs_params.exposureRows(), row
             st.exposure_step, st.exposure_lr = e["step"] + 1, e["lr"]
+        ssim_weight, depth_weight = float(np.float32(ssim_weight)), float(np.float32(depth_weight))
+        st.ssim_weight = st.depth_weight = 0.0
+        st.ref_depth_raw = st.gt_depth = st.loss_terms = st.loss_ws = None
+        if ssim_weight > 0 or depth_weight > 0:
+            n = int(lib.gps_loss_terms_workspace_floats(cam.width, cam.height))
+            if getattr(self, "_loss_ws", None) is None or self._loss_ws.numel() < n:
+                self._loss_ws = torch.empty(n, device=self.device)
+            if getattr(self, "_loss_terms", None) is None:
+                self._loss_terms = torch.zeros(4, device=self.device)
+            st.ssim_weight, st.depth_weight = ssim_weight, depth_weight
+            st.ref_depth_raw, st.depth = ref_depth.data_ptr(), self._B["depth"].data_ptr()
+            st.loss_terms, st.loss_ws = self._loss_terms.data_ptr(), self._loss_ws.data_ptr()
+            if depth_weight > 0 and gt_depth is not None:
+                gt_depth = gt_depth.to(self.device, torch.float32).contiguous()
+                st.gt_depth = gt_depth.data_ptr()
+            self._keep = self._keep + (ref_depth, gt_depth)
         o["step"] += 1
         rc = lib.gps_splat_train_step(C.byref(st), o["step"], self._stream())
         st.exposure = None   # (the struct is shared with the render path)
+        st.ssim_weight = st.depth_weight = 0.0
         check(rc, "gps_splat_train_step")  # raises on error: nothing armed
         if row >= 0:
             self._exp["step"] += 1
@@ -511,6 +533,10 @@ class RawGaussianModel:
 
     def loss_sum(self):
         return self._B["loss"]
+
+    def loss_terms(self):
+        """{total, L1 mean, 1 - mean SSIM, depth L1} of the last train_step with loss terms (None before the first one)"""
+        return getattr(self, "_loss_terms", None)
 
     def check_binning_capacity(self):
         """RawGaussianModel::checkBinningCapacity (host/raw_gs_model.cpp): blocking read-back of the binning counts.  The

@@ -125,22 +125,26 @@ PYBIND11_MODULE(_host, m) {
             return s.computeLoss(r, cam, config_from_dict(w));
         })
         .def("trainStep", [](SLAMGaussianModel& s, const Camera& cam, const torch::Tensor& ref_depth,
-                             const torch::Tensor& base_color, c10::optional<torch::Tensor> clamped, const Camera* next_cam) {
-            s.trainStep(cam, ref_depth, base_color, clamped.has_value() ? *clamped : torch::Tensor(), next_cam);
+                             const torch::Tensor& base_color, c10::optional<torch::Tensor> clamped, const Camera* next_cam,
+                             const py::dict& weights) {
+            s.trainStep(cam, ref_depth, base_color, clamped.has_value() ? *clamped : torch::Tensor(), next_cam,
+                        config_from_dict(weights));
         }, py::arg("cam"), py::arg("ref_depth"), py::arg("base_color"), py::arg("ref_depth_clamped") = py::none(),
-             py::arg("next_cam") = (const Camera*)nullptr)
+             py::arg("next_cam") = (const Camera*)nullptr, py::arg("weight_configs") = py::dict())
         .def("reserveWorkspace", &SLAMGaussianModel::reserveWorkspace)
         .def("checkBinningCapacity", &SLAMGaussianModel::checkBinningCapacity)
         .def_readonly("binning_overflows", &SLAMGaussianModel::binning_overflows)
         .def("capacity", [](SLAMGaussianModel& s) { return s.getGaussianParms().capacity(); })
         .def("adamState", [](SLAMGaussianModel& s) { return s.adamState(); })
         .def("lossSum", &SLAMGaussianModel::lossSum)
+        .def("lossTerms", &SLAMGaussianModel::lossTerms)
         .def("initOptimizers", &SLAMGaussianModel::initOptimizers, py::arg("max_iterations") = -1,
              py::arg("scene_scale") = 1.0f)
         .def("optimizersStep", &SLAMGaussianModel::optimizersStep)
         .def("optimizersZeroGrad", &SLAMGaussianModel::optimizersZeroGrad)
         .def("prunePoints", &SLAMGaussianModel::prunePoints)
         .def("grads", &SLAMGaussianModel::grads)
+        .def("leafGrads", &SLAMGaussianModel::leafGrads)
         .def("getExposure", &SLAMGaussianModel::getExposure)
         .def("exposureGrad", &SLAMGaussianModel::exposureGrad)
         .def("exposureAdamState", &SLAMGaussianModel::exposureAdamState)
@@ -300,6 +304,8 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("map_stream_kind", &SLAMPipeline::map_stream_kind)
         .def_readwrite("raycast_stream_kind", &SLAMPipeline::raycast_stream_kind)
         .def_readwrite("prefetch_next_preprocess", &SLAMPipeline::prefetch_next_preprocess)
+        .def_readwrite("fused_loss_terms", &SLAMPipeline::fused_loss_terms)
+        .def_readonly("autograd_iters", &SLAMPipeline::autograd_iters)
         .def_readwrite("frame_chain_reserve", &SLAMPipeline::frame_chain_reserve)
         .def_readwrite("pipeline_raycasts", &SLAMPipeline::pipeline_raycasts)
         .def_readwrite("merge_keyframe_raycasts", &SLAMPipeline::merge_keyframe_raycasts)

@@ -537,7 +537,7 @@ void RawGaussianModel::optimizersStep() {
 }
 
 void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_depth, const torch::Tensor& base_color,
-                                 const torch::Tensor& ref_depth_clamped, const Camera* next_cam) {
+                                 const torch::Tensor& ref_depth_clamped, const Camera* next_cam, const Config& weight_configs) {
     TORCH_CHECK(have_opt_ && adam_cap_ == opt_gs_params.capacity(), "initOptimizers() first");
     TORCH_CHECK(cam.image.defined() && cam.image.is_cuda(), "camera image must be on the device");
     applyPendingPrunes();
@@ -563,9 +563,33 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
         st.exposure_m = fptr(exp_m_); st.exposure_v = fptr(exp_v_); st.exposure_slab = fptr(exposureSlab(cam.width, cam.height));
         st.exposure_rows = (int32_t)F; st.exposure_row = row; st.exposure_step = exp_step_ + 1; st.exposure_lr = exp_lr_;
     }
+    // loss terms beyond L1 (computeLoss's weights, raw_gs_model.cpp:369-417)
+    const float ssim_w = (float)weight_configs.get("ssim_weight", 0.0), depth_w = (float)weight_configs.get("depth_weight", 0.0);
+    st.ssim_weight = st.depth_weight = 0.f;
+    st.ref_depth_raw = st.gt_depth = nullptr; st.depth = st.loss_terms = st.loss_ws = nullptr;
+    torch::Tensor gt_depth;
+    if (ssim_w > 0 || depth_w > 0) {
+        TORCH_CHECK(row < 0, "trainStep: loss terms together with an exposure row are served by forward() -> computeLoss() -> backward()");
+        check_f32_dev(ref_depth, "ref_depth");
+        const int64_t n = gps_loss_terms_workspace_floats(cam.width, cam.height);
+        if (!loss_ws_.defined() || loss_ws_.numel() < n) loss_ws_ = torch::empty({n}, f32(device));
+        if (!loss_terms_.defined()) loss_terms_ = torch::zeros({4}, f32(device));
+        st.ssim_weight = ssim_w; st.depth_weight = depth_w;
+        st.ref_depth_raw = fptr(ref_depth); st.depth = fptr(B_.depth);
+        st.loss_terms = fptr(loss_terms_); st.loss_ws = fptr(loss_ws_);
+        if (depth_w > 0 && cam.has_depth) {
+            gt_depth = cam.depth.to(device).contiguous();
+            check_f32_dev(gt_depth, "cam.depth");
+            TORCH_CHECK(gt_depth.numel() == (int64_t)cam.width * cam.height, "trainStep: cam.depth must be [H,W,1]");
+            st.gt_depth = fptr(gt_depth);
+            keep_.push_back(gt_depth);
+        }
+        keep_.push_back(ref_depth);
+    }
     adam_step_ += 1;
     const int rc = gps_splat_train_step(&st, adam_step_, current_stream());
     st.exposure = nullptr;   // (the struct is shared with the render paths)
+    st.ssim_weight = st.depth_weight = 0.f;
     check(rc, "gps_splat_train_step");   // throws on error: nothing armed then
     if (row >= 0) { exp_step_ += 1; exp_state_rows_ = opt_gs_params.exposureRows(); }
     if (ahead) prefetched_ = PrefetchKey{next_cam->pack_serial(), (int64_t)st.N, cam.width, cam.height, opt_gs_params.version()};

@@ -32,9 +32,15 @@ public:
     // next_cam (optional): the camera of the NEXT trainStep() -- its preprocessing forward then runs in the tail of this step's
     // backward + Adam kernel (gps_splat_step::next_viewmat) and that next call skips its preprocessing launch, provided it comes
     // with exactly that camera and nothing else has used the model in between (any other launch on the step buffers disarms it).
+    // weight_configs (optional; computeLoss's keys ssim_weight / depth_weight): with a non-zero weight the step carries those loss
+    // terms as well (gps_splat_step::ssim_weight ..; cam.depth is used only when cam.has_depth); lossSum() then HOLDS the total
+    // of this step and lossTerms() = {total, L1 mean, 1 - mean SSIM, depth L1}.  The empty config is the L1 step.  Not together
+    // with an exposure row of the camera (the operator route forward -> computeLoss -> backward serves that combination).
     void trainStep(const Camera& cam, const torch::Tensor& ref_depth, const torch::Tensor& base_color,
-                   const torch::Tensor& ref_depth_clamped = torch::Tensor(), const Camera* next_cam = nullptr);
+                   const torch::Tensor& ref_depth_clamped = torch::Tensor(), const Camera* next_cam = nullptr,
+                   const gpsh::Config& weight_configs = gpsh::Config());
     torch::Tensor lossSum() const { return B_.loss; }
+    torch::Tensor lossTerms() const { return loss_terms_; }   // [4], undefined before the first step with loss terms
 
     // Allocate everything an iteration at this image size needs (intermediates, Adam state) now instead of lazily on the
     // first forward / initOptimizers -- keeps one-off hipMalloc + memset time out of the frame loop.
@@ -66,6 +72,13 @@ public:
     int getGaussianNum() { return opt_gs_params.getGaussianNum(); }
     std::string getRenderMethod() const { return render_method; }
     std::vector<torch::Tensor> grads();  // gradients of the last iteration, reference parameter order
+    // the autograd route's gradients (the parameter leaves' .grad() after backward(), before optimizersZeroGrad()); undefined
+    // tensors where autograd has built no graph
+    std::vector<torch::Tensor> leafGrads() {
+        std::vector<torch::Tensor> out;
+        for (auto& t : leaf_) out.push_back(t.grad());
+        return out;
+    }
     // Adam state as [:N] views: {exp_avg x 6, exp_avg_sq x 6} in reference parameter order (empty before initOptimizers).
     // UNDEFINED between initOptimizers() and the first step: initOptimizers does not zero the buffers -- step 1 of every route
     // (gps_splat_train_step in all three fuse modes, gps_adam_step) takes m = v = 0 without reading them and writes every live row
@@ -167,6 +180,7 @@ protected:
     double exp_lr_ = 0;
     void exposureState();          // (re)size the table's optimiser buffers to the table's capacity
     torch::Tensor exposureSlab(int W, int H);
+    torch::Tensor loss_terms_, loss_ws_;   // trainStep with loss terms: the four terms and gps_loss_terms' workspace
     std::vector<torch::Tensor> leaf_;  // parameter leaves handed to autograd by the last grad-mode forward
     std::vector<torch::Tensor> keep_;  // inputs of the last launch, kept alive until the next one
     struct PendingPrune { torch::Tensor keep; int64_t n_before; };

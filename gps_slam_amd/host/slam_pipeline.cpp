@@ -202,6 +202,7 @@ void SLAMPipeline::loadConfig(const Config& c) {
     work_mode = c.gets("work_mode", work_mode);
     ssim_weight = (float)c.get("ssim_weight", ssim_weight);    // LOSS section of the configs (office0.yaml:37-39)
     depth_weight = (float)c.get("depth_weight", depth_weight);
+    fused_loss_terms = c.get("fused_loss_terms", fused_loss_terms ? 1.0 : 0.0) != 0.0;
     sample_method = c.gets("sample_method", sample_method);   // keyframe_sample_configs
     loss_thres = (float)c.get("loss_thres", loss_thres);
     TORCH_CHECK(sample_method == "random" || sample_method == "ours", "sample_method: 'random' or 'ours', got '", sample_method, "'");
@@ -544,20 +545,26 @@ void SLAMPipeline::optimizeIterations(int count) {
         TensorDict& rc = views_.raycasts[pick.first];
         waitRaycast(views_.eventOf(pick.first));
         const Camera* next_cam = nullptr;
-        if (prefetch_next_preprocess && opt_pending_ > 1 && !(ssim_weight > 0 || depth_weight > 0)) {
+        const bool terms = ssim_weight > 0 || depth_weight > 0;
+        // loss terms inside the fused step (fused_loss_terms), unless the camera has an exposure row
+        const bool fused_terms = terms && fused_loss_terms && model->exposureRow(cam) < 0;
+        if (prefetch_next_preprocess && opt_pending_ > 1 && (!terms || fused_terms)) {
             opt_peek_ = opt_loader_->getNext();
             opt_peek_valid_ = true;
             next_cam = opt_peek_.second;
         }
-        if (ssim_weight > 0 || depth_weight > 0) {
+        Config wc;
+        if (terms) { wc.num["ssim_weight"] = ssim_weight; wc.num["depth_weight"] = depth_weight; }
+        if (fused_terms) {
+            model->trainStep(cam, rc.at("depth_map"), rc.at("color_map"), rc.at("depth_map_clamped"), next_cam, wc);
+        } else if (terms) {
             // losses beyond L1: the reference's own sequence (slam_pipeline.cpp:247-254) through the autograd route
-            Config wc;
-            wc.num["ssim_weight"] = ssim_weight; wc.num["depth_weight"] = depth_weight;
             auto res = model->forward(cam, rc.at("depth_map"), rc.at("color_map"));
             auto loss = model->computeLoss(res, cam, wc);
             loss.at("total").backward();
             model->optimizersStep();
             model->optimizersZeroGrad();
+            autograd_iters++;
         } else {
             model->trainStep(cam, rc.at("depth_map"), rc.at("color_map"), rc.at("depth_map_clamped"), next_cam);
         }

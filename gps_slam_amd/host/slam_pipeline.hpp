@@ -127,6 +127,11 @@ public:
     float large_scale_thres = 0.1f, small_scale_thres = 0.003f, low_opac_thres = 0.005f;
     float scene_scale = 1.1f * 3.0f;
     float ssim_weight = 0.0f, depth_weight = 0.0f;  // both 0 in every shipped config -> the fused L1 trainStep
+    // a non-zero weight: false (default) -> the reference's sequence through autograd (forward, computeLoss, backward,
+    // optimizersStep); true -> trainStep with the weights (gps_splat_step::ssim_weight ..: one C-ABI call, next_cam prefetch
+    // allowed) for every camera without an exposure row
+    bool fused_loss_terms = false;
+    int64_t autograd_iters = 0;   // optimise iterations that went through the autograd route (forward -> computeLoss -> backward)
 
     // LOG_PIPELINE_TIME of the reference (slam_pipeline.cpp:54-67, 73-96, 141-167): host wall-clock totals of one SLAMTrainCams run in
     // milliseconds.  `per_frame` is the reference's "per frame fusion time" (ProcessFrame + pose + toGPU + updateFrameList); FPS =

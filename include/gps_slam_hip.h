@@ -300,6 +300,30 @@ GPS_API int gps_compose_l1(int width, int height, const float *render_colors, co
                    const float *base_color, const float *ref_depth_raw, const float *gt_rgb, float *rgb,
                    float *depth, float *loss, float *v_render_colors, float *v_render_alphas, gps_stream stream);
 
+/* The loss terms of computeLoss (raw_gs_model.cpp:369-417) on top of gps_compose_l1's compose, with their backward down to the
+ * rasterizer's image gradients, in two launches (no float atomics: every output is bit-identical run to run; nothing is allocated,
+ * nothing synchronises):
+ *   rgb      = (raw_rgb + base_color) / (W + 1);   depth = (raw_d + ref [ref > 0]) / (W + [ref > 0])
+ *   rgb_loss = (1 - s) mean|gt - rgb| + s (1 - mean SSIM),  s = ssim_weight  (s = 0: mean|gt - rgb|, no SSIM is computed)
+ *              SSIM: 11-tap sigma 1.5 window, zero padding, C1 = 1e-4, C2 = 9e-4, mean over the crop [5:H-5, 5:W-5] of the three
+ *              channels (padding == "valid", gsplat_wapper.hpp:664-669)
+ *   total    = rgb_loss + depth_weight mean_valid |gt_depth - depth|,  valid = gt_depth > 0 & depth > 0
+ * With no valid pixel the depth term is 0 and has a zero gradient (the reference: the mean of an empty selection, NaN, with a zero
+ * gradient).  gt_depth == NULL or depth_weight == 0: no depth term.
+ * In : render_colors[H,W,4], weight_sum[H,W], base_color[H,W,3], ref_depth_raw[H,W] (NULL iff depth is), ref_depth_clamped[H,W] and
+ *      delta_depth (pix2 only), gt_rgb[H,W,3], gt_depth[H,W] or NULL
+ * Out: rgb[H,W,3], depth[H,W] (may be NULL without a depth term), loss_terms[4] = {total, L1 mean, 1 - mean SSIM, depth L1} (stored),
+ *      loss (optional scalar: receives total), v_render_colors[H,W,4] (channel 3: the depth term's gradient), v_render_alphas[H,W],
+ *      pix2[H,W,2] = {v_render_alpha, ref_depth_clamped + delta_depth} (optional: what gps_raster_ges_bwd_strips gathers).
+ * workspace: gps_loss_terms_workspace_floats(width, height) floats (per-tile partial sums + the SSIM backward's nine maps).
+ * GPS_ERR_ARG for ssim_weight > 0 with width or height < 11. */
+GPS_API int64_t gps_loss_terms_workspace_floats(int width, int height);
+GPS_API int gps_loss_terms(int width, int height, const float *render_colors, const float *weight_sum, const float *base_color,
+                           const float *ref_depth_raw, const float *ref_depth_clamped, float delta_depth, const float *gt_rgb,
+                           const float *gt_depth, float ssim_weight, float depth_weight, float *rgb, float *depth,
+                           float *loss_terms, float *loss, float *v_render_colors, float *v_render_alphas, float *pix2,
+                           float *workspace, gps_stream stream);
+
 /* Per-frame exposure, operator level (use_exposure; raw_gs_model.cpp:331-346).  `row` is ONE camera's [3,4] row-major entry E of
  * the exposure table (device):  out[p,i] = sum_j rgb[p,j] E[i][j] + E[i][3].
  * gps_compose_exposure: gps_compose_l1's render-only call (gt_rgb NULL) with E applied to the composed colour (depth untouched):
@@ -525,6 +549,19 @@ typedef struct {
     float *v_rows, *pix2;
     int32_t *cls_ids, *cls_counts;
     int64_t cls_stride;
+    /* Loss terms beyond L1 (PIPE.weight_configs.ssim_weight / depth_weight; raw_gs_model.cpp:369-417).  All zero (the default) = off,
+     * and the step runs exactly as without these fields.  With ssim_weight > 0 or depth_weight > 0 the forward rasterizer runs its
+     * plain render instance and gps_loss_terms (two launches, below) runs between it and the backward rasterizer:
+     *   loss = (1 - ssim_weight) mean|gt - rgb| + ssim_weight (1 - mean SSIM)  +  depth_weight mean_valid|gt_depth - depth|
+     * ref_depth_raw: the UNclamped raycast depth the compose of `depth` needs; gt_depth: the frame's depth image (NULL: no depth
+     * term, whatever depth_weight says -- a camera without depth); depth[H,W] (out; required with gt_depth, otherwise optional);
+     * loss_terms[4] (out, stored): {total, L1 mean, 1 - mean SSIM, depth L1}; `loss` RECEIVES total (stored, not accumulated);
+     * loss_ws: gps_loss_terms_workspace_floats(width, height) floats.  GPS_ERR_ARG: ssim_weight > 0 with width or height < 11; a
+     * weight without `records` (the record forward); a weight together with an exposure row (hosts keep the operator route for
+     * that combination). */
+    float ssim_weight, depth_weight;
+    const float *ref_depth_raw, *gt_depth;
+    float *depth, *loss_terms, *loss_ws;
     /* Cross-iteration fusion inside an optimise loop (optional; gps_splat_can_prefetch() says whether this step supports it).
      * next_viewmat / next_Kmat / next_cam_pos != NULL in gps_splat_train_step: the camera of the NEXT iteration -- its
      * preprocessing forward (projection, SH, records, the binning's count pass) runs in the tail of this iteration's backward +
