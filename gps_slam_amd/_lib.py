@@ -61,7 +61,7 @@ class SplatStep(C.Structure):
                 [(n, vp) for n in ("ref_depth_raw", "gt_depth", "depth", "loss_terms", "loss_ws")] +
                 [(n, vp) for n in ("next_viewmat", "next_Kmat", "next_cam_pos")] + [("preprocessed", i32)] +
                 [(n, vp) for n in ("exposure", "exposure_grad", "exposure_m", "exposure_v", "exposure_slab")] +
-                [(n, i32) for n in ("exposure_rows", "exposure_row", "exposure_step")] + [("exposure_lr", f64)])
+                [(n, i32) for n in ("exposure_rows", "exposure_row", "exposure_step")] + [("exposure_lr", f64), ("exposure_terms", i32)])
 
 
 class AdamSegment(C.Structure):
@@ -103,6 +103,9 @@ PROTOTYPES = {
     "gps_adam_step": (i32, [C.POINTER(AdamSegment), i32, f64, f64, f64, i32, vp]),
     "gps_loss_terms_workspace_floats": (i64, [i32, i32]),
     "gps_loss_terms": (i32, [i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gps_loss_terms_exposure_partials": (i64, [i32, i32]),
+    "gps_loss_terms_exposure": (i32, [i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp]),
     "gps_exposure_slab_floats": (i64, [i32, i32]),
     "gps_compose_exposure": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gps_exposure_fwd": (i32, [i32, vp, vp, vp, vp]),

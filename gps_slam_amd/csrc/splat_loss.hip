@@ -12,7 +12,17 @@
 // s = 0;  total = rgb_loss + d mean_valid |gt_depth - depth|, valid = gt_depth > 0 & depth > 0.  With no valid pixel the depth term
 // is 0 with a zero gradient (the reference's value there is the mean of an empty tensor, NaN; its gradient is zero as well).
 // No float atomics, no allocation, no host synchronisation: every output is bit-identical run to run.
+//
+// The exposure instance (EXPO; use_exposure, raw_gs_model.cpp:331-346 between the compose and computeLoss): the terms are taken on
+// rgb = E(lin), lin the composed colour and E the camera's row of the exposure table.  loss_fwd_kernel then composes all three
+// channels of every halo element (each output channel reads all of them; outside the image the SSIM input stays 0, the
+// reference's zero padding of the transformed image); loss_bwd_kernel pulls d loss / d rgb back through E before the compose
+// backward and writes its tile's 12 partial sums of d loss / d E as one row of the exposure slab (plain stores, every workgroup,
+// fixed order), which gps::exposure_reduce_launch sums.
+#include <type_traits>
+
 #include "common.hpp"
+#include "splat_exposure.hpp"
 #include "splat_ssim.hpp"
 
 namespace {
@@ -43,6 +53,13 @@ struct LossArgs {
     float* maps;                   // [3 (map), 3 (channel), P]
 };
 
+struct LossArgsExposure : LossArgs {
+    const float* row;              // [3,4] of this camera
+    float* eslab;                  // [tiles, 12]: each tile workgroup's sum of d loss / d E
+};
+template <bool EXPO>
+using Args = std::conditional_t<EXPO, LossArgsExposure, LossArgs>;
+
 __device__ __forceinline__ float composed(const LossArgs& a, int c, int y, int x) {
     if (x >= a.W || y >= a.H || x < 0 || y < 0) return 0.0f;
     const int p = y * a.W + x;
@@ -50,6 +67,29 @@ __device__ __forceinline__ float composed(const LossArgs& a, int c, int y, int x
     const float den = a.weight_sum[p] + 1.0f;   // the compose of compose_l1_kernel (splat_optim.hip), operation for operation
     const float n = (c == 0 ? rc.x : (c == 1 ? rc.y : rc.z)) + a.base_color[3 * p + c];
     return n / den;
+}
+
+// gps::exposure_apply with its multiply-adds spelled out the way the compiler contracts that expression in gps_compose_exposure and
+// gps_exposure_fwd (splat_exposure.hip): left to itself it packs the three rows' products here and contracts them differently,
+// and the stage's rgb has to be the render-only forward's, bit for bit
+__device__ __forceinline__ void exposure_apply_as_composed(const float (&E)[12], float c0, float c1, float c2, float& o0, float& o1,
+                                                           float& o2) {
+    o0 = fmaf(E[2], c2, fmaf(E[0], c0, E[1] * c1)) + E[3];
+    o1 = fmaf(E[6], c2, fmaf(E[4], c0, E[5] * c1)) + E[7];
+    o2 = fmaf(E[10], c2, fmaf(E[8], c0, E[9] * c1)) + E[11];
+}
+
+// channel c of E(composed): gps_compose_exposure's arithmetic (splat_exposure.hip), operation for operation; 0 outside the image
+__device__ __forceinline__ float composed_exposure(const LossArgs& a, const float (&E)[12], int c, int y, int x) {
+    if (x >= a.W || y >= a.H || x < 0 || y < 0) return 0.0f;
+    const int p = y * a.W + x;
+    const float4 rc = a.render_colors[p];
+    const float den = a.weight_sum[p] + 1.0f;
+    const float n0 = rc.x + a.base_color[3 * p], n1 = rc.y + a.base_color[3 * p + 1], n2 = rc.z + a.base_color[3 * p + 2];
+    const float c0 = n0 / den, c1 = n1 / den, c2 = n2 / den;
+    float e0, e1, e2;
+    exposure_apply_as_composed(E, c0, c1, c2, e0, e1, e2);
+    return c == 0 ? e0 : (c == 1 ? e1 : e2);
 }
 
 __device__ __forceinline__ float image_at(const float* __restrict__ img, int c, int y, int x, int H, int W) {
@@ -71,18 +111,35 @@ __device__ __forceinline__ void block_sum4(float (&v)[SLAB_ROW], float* red /* L
         v[k] = ((red[k] + red[SLAB_ROW + k]) + red[2 * SLAB_ROW + k]) + red[3 * SLAB_ROW + k];
 }
 
-template <bool SSIM>
-__global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(LossArgs a) {
+// 12 per-thread values -> workgroup sum k returned in thread k < 12: butterfly sums inside each wave, then the four waves in order
+__device__ __forceinline__ float block_sum12(float (&v)[12], float* red /* LDS [4][12] */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 12; k++) v[k] = wave_sum(v[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) red[wave * 12 + k] = v[k];
+    }
+    __syncthreads();
+    const int k = threadIdx.x < 12 ? threadIdx.x : 0;
+    return ((red[k] + red[12 + k]) + red[24 + k]) + red[36 + k];
+}
+
+template <bool SSIM, bool EXPO = false>
+__global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(Args<EXPO> a) {
     __shared__ float ta[SSIM ? TIN : 1][LD_IN], tb[SSIM ? TIN : 1][LD_IN];
     __shared__ float h[SSIM ? 5 : 1][TIN][SSIM ? LD_H : 1];
     __shared__ float red[4 * SLAB_ROW];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TS, y0 = blockIdx.y * TS, c = blockIdx.z;
     const int W = a.W, H = a.H;
+    [[maybe_unused]] float E[EXPO ? 12 : 1];
+    if constexpr (EXPO) gps::exposure_load(a.row, E);
     if constexpr (SSIM) {
         for (int q = tid; q < TIN * TIN; q += LOSS_THREADS) {
             const int ly = q / TIN, lx = q - ly * TIN;
-            ta[ly][lx] = composed(a, c, y0 + ly - HALO, x0 + lx - HALO);
+            if constexpr (EXPO) ta[ly][lx] = composed_exposure(a, E, c, y0 + ly - HALO, x0 + lx - HALO);
+            else ta[ly][lx] = composed(a, c, y0 + ly - HALO, x0 + lx - HALO);
             tb[ly][lx] = image_at(a.gt_rgb, c, y0 + ly - HALO, x0 + lx - HALO, H, W);
         }
         __syncthreads();
@@ -101,7 +158,10 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(LossArgs a) {
         if constexpr (SSIM) ypass5(h, ly, lx, mu1, e11, mu2, e22, e12);
         if (x >= W || y >= H) continue;
         const int p = y * W + x;
-        const float col = SSIM ? ta[ly + HALO][lx + HALO] : composed(a, c, y, x);
+        float col;
+        if constexpr (SSIM) col = ta[ly + HALO][lx + HALO];
+        else if constexpr (EXPO) col = composed_exposure(a, E, c, y, x);
+        else col = composed(a, c, y, x);
         a.rgb[3 * p + c] = col;
         acc[0] += fabsf(a.gt_rgb[3 * p + c] - col);
         if constexpr (SSIM) {
@@ -131,8 +191,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(LossArgs a) {
     }
 }
 
-template <bool SSIM>
-__global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a) {
+template <bool SSIM, bool EXPO = false>
+__global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(Args<EXPO> a) {
     __shared__ float t[SSIM ? 3 : 1][TIN][SSIM ? LD_IN : 1];
     __shared__ float h[SSIM ? 3 : 1][TIN][SSIM ? LD_H : 1];
     __shared__ double dred[LOSS_THREADS][SLAB_ROW];
@@ -216,6 +276,12 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a) {
             g[j][c] = gc;
         }
     }
+    [[maybe_unused]] float E[EXPO ? 12 : 1], ve[EXPO ? 12 : 1];
+    if constexpr (EXPO) {
+        gps::exposure_load(a.row, E);
+#pragma unroll
+        for (int k = 0; k < 12; k++) ve[k] = 0.f;
+    }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int q = tid + j * LOSS_THREADS;
@@ -228,6 +294,12 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a) {
         const float den = w + 1.0f;
         const float n0 = rc.x + a.base_color[3 * p], n1 = rc.y + a.base_color[3 * p + 1], n2 = rc.z + a.base_color[3 * p + 2];
         const float dd = den * den;
+        if constexpr (EXPO) {   // g: d loss / d E(lin) -> d loss / d E, then d loss / d lin
+            gps::exposure_grad_acc(ve, g[j][0], g[j][1], g[j][2], n0 / den, n1 / den, n2 / den);
+            float v0, v1, v2;
+            gps::exposure_vjp(E, g[j][0], g[j][1], g[j][2], v0, v1, v2);
+            g[j][0] = v0; g[j][1] = v1; g[j][2] = v2;
+        }
         float va = -(g[j][0] * n0) / dd - (g[j][1] * n1) / dd - (g[j][2] * n2) / dd;
         float v3 = 0.f;
         if (g_depth > 0.f) {
@@ -247,6 +319,11 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a) {
         // what the strip backward gathers per pixel: {d loss / d weight sum, the depth cut ref_depth + delta_depth}
         if (a.pix2) a.pix2[p] = make_float2(va, a.ref_depth_clamped[p] + a.delta_depth);
     }
+    if constexpr (EXPO) {   // this tile's row of the exposure slab (every launched tile holds a pixel)
+        __syncthreads();    // dred is consumed: its memory holds the four waves' sums
+        const float tot = block_sum12(ve, reinterpret_cast<float*>(&dred[0][0]));
+        if (tid < 12) a.eslab[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 12 + tid] = tot;
+    }
 }
 
 }  // namespace
@@ -259,10 +336,12 @@ int64_t gps_loss_terms_workspace_floats(int width, int height) {
     return tiles * 3 * SLAB_ROW + 9 * (int64_t)width * height;
 }
 
-int gps_loss_terms(int width, int height, const float* render_colors, const float* weight_sum, const float* base_color,
-                   const float* ref_depth_raw, const float* ref_depth_clamped, float delta_depth, const float* gt_rgb,
-                   const float* gt_depth, float ssim_weight, float depth_weight, float* rgb, float* depth, float* loss_terms,
-                   float* loss, float* v_render_colors, float* v_render_alphas, float* pix2, float* workspace, gps_stream stream) {
+// row == NULL: the plain instances; otherwise the exposure instances, which also write eslab[tiles, 12]
+static int loss_terms_launch(int width, int height, const float* render_colors, const float* weight_sum, const float* base_color,
+                             const float* ref_depth_raw, const float* ref_depth_clamped, float delta_depth, const float* gt_rgb,
+                             const float* gt_depth, float ssim_weight, float depth_weight, float* rgb, float* depth,
+                             float* loss_terms, float* loss, float* v_render_colors, float* v_render_alphas, float* pix2,
+                             float* workspace, const float* row, float* eslab, gps_stream stream) {
     GPS_ENTER();
     GPS_REQUIRE(width > 0 && height > 0 && (int64_t)width * height <= (int64_t)1 << 26);
     GPS_REQUIRE(render_colors && weight_sum && base_color && gt_rgb && rgb && loss_terms && v_render_colors && v_render_alphas &&
@@ -278,7 +357,20 @@ int gps_loss_terms(int width, int height, const float* render_colors, const floa
                   depth_weight > 0.f ? gt_depth : nullptr, ssim_weight, depth_weight, delta_depth, rgb, depth, loss_terms, loss,
                   (float4*)v_render_colors, v_render_alphas, (float2*)pix2, slab, slab + (size_t)tiles.x * tiles.y * 3 * SLAB_ROW};
     hipStream_t s = (hipStream_t)stream;
-    if (ssim_weight > 0.f) {
+    if (row) {
+        LossArgsExposure ae;
+        static_cast<LossArgs&>(ae) = a;
+        ae.row = row; ae.eslab = eslab;
+        if (ssim_weight > 0.f) {
+            loss_fwd_kernel<true, true><<<dim3(tiles.x, tiles.y, 3), LOSS_THREADS, 0, s>>>(ae);
+            GPS_LAUNCH_CHECK();
+            loss_bwd_kernel<true, true><<<tiles, LOSS_THREADS, 0, s>>>(ae);
+        } else {
+            loss_fwd_kernel<false, true><<<dim3(tiles.x, tiles.y, 3), LOSS_THREADS, 0, s>>>(ae);
+            GPS_LAUNCH_CHECK();
+            loss_bwd_kernel<false, true><<<tiles, LOSS_THREADS, 0, s>>>(ae);
+        }
+    } else if (ssim_weight > 0.f) {
         loss_fwd_kernel<true><<<dim3(tiles.x, tiles.y, 3), LOSS_THREADS, 0, s>>>(a);
         GPS_LAUNCH_CHECK();
         loss_bwd_kernel<true><<<tiles, LOSS_THREADS, 0, s>>>(a);
@@ -289,6 +381,31 @@ int gps_loss_terms(int width, int height, const float* render_colors, const floa
     }
     GPS_LAUNCH_CHECK();
     return GPS_OK;
+}
+
+int gps_loss_terms(int width, int height, const float* render_colors, const float* weight_sum, const float* base_color,
+                   const float* ref_depth_raw, const float* ref_depth_clamped, float delta_depth, const float* gt_rgb,
+                   const float* gt_depth, float ssim_weight, float depth_weight, float* rgb, float* depth, float* loss_terms,
+                   float* loss, float* v_render_colors, float* v_render_alphas, float* pix2, float* workspace, gps_stream stream) {
+    return loss_terms_launch(width, height, render_colors, weight_sum, base_color, ref_depth_raw, ref_depth_clamped, delta_depth,
+                             gt_rgb, gt_depth, ssim_weight, depth_weight, rgb, depth, loss_terms, loss, v_render_colors,
+                             v_render_alphas, pix2, workspace, nullptr, nullptr, stream);
+}
+
+int64_t gps_loss_terms_exposure_partials(int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    return (int64_t)gps_div_up(width, TS) * gps_div_up(height, TS);
+}
+
+int gps_loss_terms_exposure(int width, int height, const float* render_colors, const float* weight_sum, const float* base_color,
+                            const float* ref_depth_raw, const float* ref_depth_clamped, float delta_depth, const float* gt_rgb,
+                            const float* gt_depth, float ssim_weight, float depth_weight, float* rgb, float* depth,
+                            float* loss_terms, float* loss, float* v_render_colors, float* v_render_alphas, float* pix2,
+                            float* workspace, const float* row, float* slab, gps_stream stream) {
+    GPS_REQUIRE(row && slab);
+    return loss_terms_launch(width, height, render_colors, weight_sum, base_color, ref_depth_raw, ref_depth_clamped, delta_depth,
+                             gt_rgb, gt_depth, ssim_weight, depth_weight, rgb, depth, loss_terms, loss, v_render_colors,
+                             v_render_alphas, pix2, workspace, row, slab, stream);
 }
 
 }  // extern "C"

@@ -97,13 +97,14 @@ int gps_splat_train_step(const gps_splat_step* a, int adam_step, gps_stream stre
     // gradients), expand, count table, row scan, scatter, forward, group backward, preprocess backward.
     GPS_REQUIRE(a->base_color != nullptr);
     // loss terms beyond L1 (ssim_weight / depth_weight): the forward rasterizer's plain render instance, then gps_loss_terms
-    // (splat_loss.hip: two launches) writes what the compose epilogue writes otherwise
+    // (splat_loss.hip: two launches) writes what the compose epilogue writes otherwise; with an exposure row (exposure_terms)
+    // gps_loss_terms_exposure, which also writes the exposure slab the rasterizer's exposure instance writes otherwise
     const bool terms = a->ssim_weight > 0.f || a->depth_weight > 0.f;
     GPS_REQUIRE(a->ssim_weight >= 0.f && a->depth_weight >= 0.f);
     if (terms) {
         GPS_REQUIRE(a->records && a->rgb && a->loss_terms && a->loss_ws);
         GPS_REQUIRE(!(a->ssim_weight > 0.f) || (a->width >= 11 && a->height >= 11));
-        GPS_REQUIRE(!(a->exposure && a->exposure_row >= 0 && a->exposure_row < a->exposure_rows));
+        GPS_REQUIRE(a->exposure_terms != 0 || !(a->exposure && a->exposure_row >= 0 && a->exposure_row < a->exposure_rows));
         GPS_REQUIRE(!(a->depth_weight > 0.f && a->gt_depth) || (a->depth && a->ref_depth_raw));
     }
     const bool fused_fwd = a->records != nullptr;  // the record rasterizer carries the compose epilogue
@@ -122,14 +123,24 @@ int gps_splat_train_step(const gps_splat_step* a, int adam_step, gps_stream stre
         GPS_REQUIRE(fused_fwd && a->exposure_grad && a->exposure_m && a->exposure_v && a->exposure_slab && a->exposure_step >= 1);
         ex = {a->exposure + 12 * (size_t)a->exposure_row, a->exposure_slab};
     }
-    int r = render_chain(a, fused_fwd && !terms ? &fc : nullptr, strips ? &no_zero : &zg, stream, a->preprocessed != 0, expo ? &ex : nullptr);
+    int r = render_chain(a, fused_fwd && !terms ? &fc : nullptr, strips ? &no_zero : &zg, stream, a->preprocessed != 0,
+                         expo && !terms ? &ex : nullptr);
     if (r != GPS_OK) return r;
     if (!fused_fwd) {
         r = gps_compose_l1(a->width, a->height, a->render_colors, a->weight_sum, a->base_color, nullptr, a->gt_rgb, a->rgb,
                            nullptr, a->loss, a->v_render_colors, a->v_render_alphas, stream);
         if (r != GPS_OK) return r;
     }
-    if (terms) {
+    int exposure_partials = gps_div_up(a->width, 16) * gps_div_up(a->height, 16);   // one slab row per rasterizer tile
+    if (terms && expo) {
+        r = gps_loss_terms_exposure(a->width, a->height, a->render_colors, a->weight_sum, a->base_color,
+                                    a->depth ? a->ref_depth_raw : nullptr, a->ref_depth_clamped, a->delta_depth, a->gt_rgb, a->gt_depth,
+                                    a->ssim_weight, a->depth_weight, a->rgb, a->ref_depth_raw ? a->depth : nullptr, a->loss_terms,
+                                    a->loss, a->v_render_colors, a->v_render_alphas, strips ? a->pix2 : nullptr, a->loss_ws, ex.row,
+                                    ex.slab, stream);
+        if (r != GPS_OK) return r;
+        exposure_partials = (int)gps_loss_terms_exposure_partials(a->width, a->height);   // one per loss-stage tile
+    } else if (terms) {
         r = gps_loss_terms(a->width, a->height, a->render_colors, a->weight_sum, a->base_color, a->depth ? a->ref_depth_raw : nullptr,
                            a->ref_depth_clamped, a->delta_depth, a->gt_rgb, a->gt_depth, a->ssim_weight, a->depth_weight, a->rgb,
                            a->ref_depth_raw ? a->depth : nullptr, a->loss_terms, a->loss, a->v_render_colors, a->v_render_alphas,
@@ -141,9 +152,8 @@ int gps_splat_train_step(const gps_splat_step* a, int adam_step, gps_stream stre
         // wrote).  Folding it into a later launch would put a dependent tail into the default instances of the backward kernels
         // (changing their code) for 12 x rows floats of work; as a launch of its own it leaves every default kernel as it is.
         const gps::AdamScalars es = gps::adam_scalars(a->exposure_lr, a->beta1, a->beta2, a->adam_eps, a->exposure_step);
-        const int tiles = gps_div_up(a->width, 16) * gps_div_up(a->height, 16);
-        r = gps::exposure_reduce_launch(a->exposure_slab, tiles, a->exposure_rows, a->exposure_row, a->exposure_grad, a->exposure,
-                                        a->exposure_m, a->exposure_v, &es, stream);
+        r = gps::exposure_reduce_launch(a->exposure_slab, exposure_partials, a->exposure_rows, a->exposure_row, a->exposure_grad,
+                                        a->exposure, a->exposure_m, a->exposure_v, &es, stream);
         if (r != GPS_OK) return r;
     }
     if (strips)

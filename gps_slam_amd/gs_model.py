@@ -476,8 +476,9 @@ class RawGaussianModel:
         the one thing this cannot see); ignored where the step cannot prefetch.
         ssim_weight / depth_weight (computeLoss's weights, raw_gs_model.cpp:369-417; gt_depth: the frame's depth [H,W,1] or None
         for a camera without one): with a non-zero weight the step carries those loss terms as well (gps_splat_step::ssim_weight
-        ..); loss_sum() then HOLDS this step's total and loss_terms() = {total, L1 mean, 1 - mean SSIM, depth L1}.  Not together
-        with an exposure row of the camera (gps_splat_train_step refuses it)."""
+        ..); loss_sum() then HOLDS this step's total and loss_terms() = {total, L1 mean, 1 - mean SSIM, depth L1}.  For a camera
+        with an exposure row the terms are taken on E(rgb) and the table is stepped in the same call
+        (gps_splat_step::exposure_terms)."""
         if ref_depth_clamped is None:
             ref_depth_clamped = self.clamp_ref_depth(ref_depth)
         st = self._step_struct(cam.width, cam.height)
@@ -498,7 +499,7 @@ class RawGaussianModel:
             raise RuntimeError("initOptimizers() first")
         row = self.exposure_row(cam)
         st.exposure = st.exposure_grad = st.exposure_m = st.exposure_v = st.exposure_slab = None
-        st.exposure_rows, st.exposure_row, st.exposure_step, st.exposure_lr = 0, -1, 0, 0.0
+        st.exposure_rows, st.exposure_row, st.exposure_step, st.exposure_lr, st.exposure_terms = 0, -1, 0, 0.0, 0
         if row >= 0:   # the camera has a row: the table is stepped in this call (its own step count)
             e = self._exposure_state(cam.width, cam.height)
             st.exposure, st.exposure_grad = self.opt_gs_params._exp_buf.data_ptr(), e["g"].data_ptr()
@@ -515,6 +516,7 @@ class RawGaussianModel:
             if getattr(self, "_loss_terms", None) is None:
                 self._loss_terms = torch.zeros(4, device=self.device)
             st.ssim_weight, st.depth_weight = ssim_weight, depth_weight
+            st.exposure_terms = 1 if row >= 0 else 0
             st.ref_depth_raw, st.depth = ref_depth.data_ptr(), self._B["depth"].data_ptr()
             st.loss_terms, st.loss_ws = self._loss_terms.data_ptr(), self._loss_ws.data_ptr()
             if depth_weight > 0 and gt_depth is not None:
@@ -524,6 +526,7 @@ class RawGaussianModel:
         o["step"] += 1
         rc = lib.gps_splat_train_step(C.byref(st), o["step"], self._stream())
         st.exposure = None   # (the struct is shared with the render path)
+        st.exposure_terms = 0
         st.ssim_weight = st.depth_weight = 0.0
         check(rc, "gps_splat_train_step")  # raises on error: nothing armed
         if row >= 0:

@@ -554,7 +554,7 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
     if (ahead) { st.next_viewmat = next_cam->viewmat(); st.next_Kmat = next_cam->Kmat(); st.next_cam_pos = next_cam->cam_pos(); }
     const int row = exposureRow(cam);
     st.exposure = nullptr; st.exposure_grad = st.exposure_m = st.exposure_v = st.exposure_slab = nullptr;
-    st.exposure_rows = 0; st.exposure_row = -1; st.exposure_step = 0; st.exposure_lr = 0;
+    st.exposure_rows = 0; st.exposure_row = -1; st.exposure_step = 0; st.exposure_lr = 0; st.exposure_terms = 0;
     if (row >= 0) {   // the camera has a row: the table is stepped in this call (its own count)
         exposureState();
         const int64_t F = opt_gs_params.exposureRows();
@@ -569,7 +569,7 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
     st.ref_depth_raw = st.gt_depth = nullptr; st.depth = st.loss_terms = st.loss_ws = nullptr;
     torch::Tensor gt_depth;
     if (ssim_w > 0 || depth_w > 0) {
-        TORCH_CHECK(row < 0, "trainStep: loss terms together with an exposure row are served by forward() -> computeLoss() -> backward()");
+        st.exposure_terms = row >= 0 ? 1 : 0;   // the terms on E(rgb), the table stepped in the same call
         check_f32_dev(ref_depth, "ref_depth");
         const int64_t n = gps_loss_terms_workspace_floats(cam.width, cam.height);
         if (!loss_ws_.defined() || loss_ws_.numel() < n) loss_ws_ = torch::empty({n}, f32(device));
@@ -588,7 +588,7 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
     }
     adam_step_ += 1;
     const int rc = gps_splat_train_step(&st, adam_step_, current_stream());
-    st.exposure = nullptr;   // (the struct is shared with the render paths)
+    st.exposure = nullptr; st.exposure_terms = 0;   // (the struct is shared with the render paths)
     st.ssim_weight = st.depth_weight = 0.f;
     check(rc, "gps_splat_train_step");   // throws on error: nothing armed then
     if (row >= 0) { exp_step_ += 1; exp_state_rows_ = opt_gs_params.exposureRows(); }

@@ -546,8 +546,8 @@ void SLAMPipeline::optimizeIterations(int count) {
         waitRaycast(views_.eventOf(pick.first));
         const Camera* next_cam = nullptr;
         const bool terms = ssim_weight > 0 || depth_weight > 0;
-        // loss terms inside the fused step (fused_loss_terms), unless the camera has an exposure row
-        const bool fused_terms = terms && fused_loss_terms && model->exposureRow(cam) < 0;
+        // loss terms inside the fused step (fused_loss_terms), with or without an exposure row of the camera
+        const bool fused_terms = terms && fused_loss_terms;
         if (prefetch_next_preprocess && opt_pending_ > 1 && (!terms || fused_terms)) {
             opt_peek_ = opt_loader_->getNext();
             opt_peek_valid_ = true;

@@ -323,6 +323,20 @@ GPS_API int gps_loss_terms(int width, int height, const float *render_colors, co
                            const float *gt_depth, float ssim_weight, float depth_weight, float *rgb, float *depth,
                            float *loss_terms, float *loss, float *v_render_colors, float *v_render_alphas, float *pix2,
                            float *workspace, gps_stream stream);
+/* gps_loss_terms for a camera with a row in the exposure table (use_exposure; raw_gs_model.cpp:331-346 between the compose and
+ * computeLoss): the terms are taken on rgb[i] = sum_j lin[j] E[i][j] + E[i][3], lin the compose above and E = row[3][4] (ONE camera's
+ * entry, device; as gps_compose_exposure writes it, bit for bit); the SSIM window sees 0 outside the image; depth and its term do
+ * not depend on E.  v_render_colors / v_render_alphas / pix2 carry the gradient pulled back through E, and every 32 x 32 tile
+ * workgroup stores its 12 partial sums of d loss / d E = sum_p g[p] (x) [lin[p], 1] as one row of slab[partials, 12] (plain stores,
+ * fixed order: bit-identical run to run), partials = gps_loss_terms_exposure_partials(width, height) = ceil(W/32) ceil(H/32): the
+ * n_partials of gps_exposure_reduce.  The slab fits gps_exposure_slab_floats(width, height); the workspace is gps_loss_terms'. */
+GPS_API int64_t gps_loss_terms_exposure_partials(int width, int height);
+GPS_API int gps_loss_terms_exposure(int width, int height, const float *render_colors, const float *weight_sum,
+                                    const float *base_color, const float *ref_depth_raw, const float *ref_depth_clamped,
+                                    float delta_depth, const float *gt_rgb, const float *gt_depth, float ssim_weight,
+                                    float depth_weight, float *rgb, float *depth, float *loss_terms, float *loss,
+                                    float *v_render_colors, float *v_render_alphas, float *pix2, float *workspace, const float *row,
+                                    float *slab, gps_stream stream);
 
 /* Per-frame exposure, operator level (use_exposure; raw_gs_model.cpp:331-346).  `row` is ONE camera's [3,4] row-major entry E of
  * the exposure table (device):  out[p,i] = sum_j rgb[p,j] E[i][j] + E[i][3].
@@ -557,8 +571,8 @@ typedef struct {
      * term, whatever depth_weight says -- a camera without depth); depth[H,W] (out; required with gt_depth, otherwise optional);
      * loss_terms[4] (out, stored): {total, L1 mean, 1 - mean SSIM, depth L1}; `loss` RECEIVES total (stored, not accumulated);
      * loss_ws: gps_loss_terms_workspace_floats(width, height) floats.  GPS_ERR_ARG: ssim_weight > 0 with width or height < 11; a
-     * weight without `records` (the record forward); a weight together with an exposure row (hosts keep the operator route for
-     * that combination). */
+     * weight without `records` (the record forward); a weight together with an exposure row unless exposure_terms (below) asks
+     * for that combination. */
     float ssim_weight, depth_weight;
     const float *ref_depth_raw, *gt_depth;
     float *depth, *loss_terms, *loss_ws;
@@ -578,10 +592,15 @@ typedef struct {
      * rasterizer and the backward (it needs only the slab; the backward does not read the table): the fixed-order slab sum,
      * exposure_grad := the full-table gradient (zero outside row r) and an Adam step number exposure_step (1-based, counted apart
      * from adam_step) of the whole table with exposure_lr and beta1 / beta2 / adam_eps above (exposure_m / exposure_v: its moments,
-     * [exposure_rows, 3, 4]).  Otherwise the table is neither read nor stepped.  Needs the record forward (records != NULL). */
+     * [exposure_rows, 3, 4]).  Otherwise the table is neither read nor stepped.  Needs the record forward (records != NULL).
+     * exposure_terms != 0: a weight above together with an exposure row is served as well -- the forward rasterizer runs its plain
+     * render instance, gps_loss_terms_exposure takes the terms on E[r](rgb) and writes one slab row per 32 x 32 tile, and the same
+     * reduce + Adam launch follows.  0 (the default): that combination is GPS_ERR_ARG before anything is launched.  Hosts set it
+     * for the one call and clear it afterwards. */
     float *exposure, *exposure_grad, *exposure_m, *exposure_v, *exposure_slab;
     int32_t exposure_rows, exposure_row, exposure_step;
     double exposure_lr;
+    int32_t exposure_terms;
 } gps_splat_step;
 
 /* != 0: gps_splat_train_step(a) can run the next iteration's preprocessing in its tail (strip backward + superblock binning in
