@@ -159,6 +159,10 @@ PROTOTYPES = {
     "gps_knn_mean_dist2": (i32, [i32, vp, vp, vp]),
     "gps_knn_grid_workspace_bytes": (i64, [i32]),
     "gps_knn_mean_dist2_grid": (i32, [i32, vp, vp, vp, i64, vp]),
+    "gps_nn_index_workspace_bytes": (i64, [i32]),
+    "gps_nn_index_build": (i32, [i32, vp, vp, i64, vp]),
+    "gps_nn_query_workspace_bytes": (i64, [i32]),
+    "gps_nn_query": (i32, [i32, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
     "gps_normal_map": (i32, [i32, i32, vp, vp, vp]),
     "gps_zero_floats": (i32, [i32, vp, vp, vp]),
     "gps_rgba8_to_rgbf": (i32, [i32, vp, vp, vp]),

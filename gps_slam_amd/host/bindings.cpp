@@ -157,6 +157,39 @@ PYBIND11_MODULE(_host, m) {
         .def("addGaussians", [](SLAMGaussianModel& s, const Camera& cam, const TensorDict& maps, const torch::Tensor& mask,
                                 float ratio, int frame_num) { return s.addGaussians(cam, maps, mask, ratio, frame_num); });
 
+    // ---- geometry / trajectory evaluation (geom_eval.hpp)
+    py::class_<GeomEvalResult>(m, "GeomEvalResult")
+        .def_readonly("accuracy_cm", &GeomEvalResult::accuracy_cm)
+        .def_readonly("completion_cm", &GeomEvalResult::completion_cm)
+        .def_readonly("dist_thres", &GeomEvalResult::dist_thres)
+        .def_readonly("accuracy_ratio", &GeomEvalResult::accuracy_ratio)
+        .def_readonly("completion_ratio", &GeomEvalResult::completion_ratio)
+        .def_readonly("f1", &GeomEvalResult::f1)
+        .def_readonly("n_rec", &GeomEvalResult::n_rec)
+        .def_readonly("n_gt", &GeomEvalResult::n_gt);
+    py::class_<AteResult>(m, "AteResult")
+        .def_readonly("ate_mean_cm", &AteResult::ate_mean_cm)
+        .def_readonly("ate_rmse_cm", &AteResult::ate_rmse_cm)
+        .def_readonly("trans_error", &AteResult::trans_error)
+        .def_readonly("rot", &AteResult::rot)
+        .def_readonly("trans", &AteResult::trans);
+    m.def("nearestDistances", [](const torch::Tensor& q, const torch::Tensor& r) { return nearestDistances(q, r); }, py::arg("query"), py::arg("ref"));
+    m.def("nearestDistancesStats", [](const torch::Tensor& q, const torch::Tensor& r) {
+        torch::Tensor stats;
+        auto out = nearestDistances(q, r, &stats);
+        return std::make_tuple(out.first, out.second, stats);
+    }, py::arg("query"), py::arg("ref"));
+    m.def("surfaceUniforms", &surfaceUniforms, py::arg("n"), py::arg("seed"));
+    m.def("sampleSurface", [](const torch::Tensor& tri, int64_t n, uint64_t seed, const c10::optional<torch::Tensor>& u) {
+        return sampleSurface(tri, n, seed, u ? *u : torch::Tensor());
+    }, py::arg("triangles"), py::arg("n"), py::arg("seed") = 0, py::arg("uniforms") = py::none());
+    m.def("evalPointClouds", [](const torch::Tensor& rec, const torch::Tensor& gt, const c10::optional<torch::Tensor>& T,
+                                const std::vector<double>& th, int64_t sample_nums, uint64_t seed) {
+        return evalPointClouds(rec, gt, T ? *T : torch::Tensor(), th, sample_nums, seed);
+    }, py::arg("rec_points"), py::arg("gt_points"), py::arg("transform") = py::none(), py::arg("dist_thres") = std::vector<double>{0.03},
+          py::arg("sample_nums") = 1000000, py::arg("seed") = 0);
+    m.def("ate", &ate, py::arg("est_c2w"), py::arg("gt_c2w"));
+
     // ---- TSDF engine
     py::class_<TsdfEngine>(m, "ITMBasicEngine")
         .def(py::init([](int w, int h, float fx, float fy, float cx, float cy, float voxel_size, float mu, float vmin,
@@ -202,6 +235,11 @@ PYBIND11_MODULE(_host, m) {
         .def("getVoxelSize", &TsdfEngine::getVoxelSize)
         .def("counters", &TsdfEngine::counters)
         .def("MeshScene", &TsdfEngine::MeshScene, py::arg("maxTriangles") = (int64_t)1 << 24)
+        .def("EvalMesh", [](TsdfEngine& e, const torch::Tensor& gt, const c10::optional<torch::Tensor>& T, const std::vector<double>& th,
+                            int64_t sample_nums, uint64_t seed, int64_t m) {
+            return e.EvalMesh(gt, T ? *T : torch::Tensor(), th, sample_nums, seed, m);
+        }, py::arg("gt_points_or_triangles"), py::arg("transform") = py::none(), py::arg("dist_thres") = std::vector<double>{0.03},
+             py::arg("sample_nums") = 1000000, py::arg("seed") = 0, py::arg("maxTriangles") = (int64_t)1 << 24)
         .def("SaveSceneToMesh", [](TsdfEngine& e, const std::string& f, int64_t m) { return e.SaveSceneToMesh(f.c_str(), m); },
              py::arg("fileName"), py::arg("maxTriangles") = (int64_t)1 << 24)
         .def("SaveToFile", &TsdfEngine::SaveToFile)
@@ -343,6 +381,13 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("saved_engine", &SLAMPipeline::saved_engine)
         .def("renderEvalImgs", &SLAMPipeline::renderEvalImgs, py::arg("cams"), py::arg("names") = std::vector<std::string>{"rgb"},
              py::call_guard<py::gil_scoped_release>())
+        .def("evalGeometry", [](SLAMPipeline& p, const torch::Tensor& gt, const c10::optional<torch::Tensor>& T, const std::vector<double>& th,
+                                int64_t sample_nums, uint64_t seed) {
+            py::gil_scoped_release nogil;
+            return p.evalGeometry(gt, T ? *T : torch::Tensor(), th, sample_nums, seed);
+        }, py::arg("gt_points_or_triangles"), py::arg("transform") = py::none(), py::arg("dist_thres") = std::vector<double>{0.03},
+             py::arg("sample_nums") = 1000000, py::arg("seed") = 0)
+        .def("evalTrajectory", &SLAMPipeline::evalTrajectory, py::call_guard<py::gil_scoped_release>())
         .def("saveMesh", &SLAMPipeline::saveMesh)
         .def("saveEngine", &SLAMPipeline::saveEngine)
         .def("loadEngine", &SLAMPipeline::loadEngine)

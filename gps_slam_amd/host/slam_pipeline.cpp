@@ -634,12 +634,39 @@ std::vector<TensorDict> SLAMPipeline::renderEvalImgs(const std::vector<Camera>& 
     return out;
 }
 
+// ------------------------------------------------------------------ geometry / trajectory evaluation (geom_eval.hpp)
+GeomEvalResult SLAMPipeline::evalGeometry(const torch::Tensor& gt, const torch::Tensor& transform, const std::vector<double>& dist_thres,
+                                          int64_t sample_nums, uint64_t seed) {
+    flush();
+    requireEngine("evalGeometry");
+    return main_engine->EvalMesh(gt, transform, dist_thres, sample_nums, seed);
+}
+
+AteResult SLAMPipeline::evalTrajectory() {
+    flush();
+    requireEngine("evalTrajectory");
+    const auto& est = main_engine->camPoses;
+    const auto& gt = main_engine->gtC2wPoses;
+    TORCH_CHECK(est.size() == gt.size(), "evalTrajectory: ", est.size(), " stored poses against ", gt.size(), " ground-truth poses");
+    TORCH_CHECK(est.size() >= 3, "evalTrajectory: at least three frames are needed");
+    const int64_t n = (int64_t)est.size();
+    auto e = torch::empty({n, 4, 4}, torch::kFloat64), g = torch::empty({n, 4, 4}, torch::kFloat64);
+    for (int64_t i = 0; i < n; i++) {
+        const float* invM = est[i].GetInvM();   // ORUtils layout (column-major) -> row-major c2w
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) e[i][r][c] = (double)invM[4 * c + r];
+        g[i] = gt[i].to(torch::kCPU, torch::kFloat64).reshape({4, 4});
+    }
+    return ate(e, g);
+}
+
 // ------------------------------------------------------------------ one SLAM frame (body of SLAMTrainCams :69-132)
 void SLAMPipeline::processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16) {
     curr_frame_id = i;
     const double tt0 = now_ms();
     gate_wait_ms_ = handover_wait_ms_ = 0.0;
-    if (!main_engine->trackingActive && (int)main_engine->gtC2wPoses.size() <= main_engine->framesProcessed)
+    // (with the tracker on the engine does not read them: kept for evalTrajectory)
+    if ((!main_engine->trackingActive || cam.c2w.defined()) && (int)main_engine->gtC2wPoses.size() <= main_engine->framesProcessed)
         main_engine->gtC2wPoses.push_back(cam.c2w);
     ITMTrackingState* ts;
     torch::Tensor frame_rgba;

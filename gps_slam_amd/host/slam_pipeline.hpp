@@ -99,6 +99,13 @@ public:
     void saveEngine() { if (!saved_engine.empty()) main_engine->SaveToFile(workspace_dir + "/" + saved_engine); }
     void loadEngine() { main_engine->LoadFromFile(workspace_dir + "/" + saved_engine); }
 
+    // The reference's other two result numbers (scripts/geo_general.py, scripts/ate_general.py) on the run so far; both flush()
+    // first and need an attached engine.  evalGeometry: TsdfEngine::EvalMesh.  evalTrajectory: ate() of the engine's stored
+    // per-frame poses (camPoses) against gtC2wPoses; mismatched lengths or fewer than three frames throw.
+    GeomEvalResult evalGeometry(const torch::Tensor& gt_points_or_triangles, const torch::Tensor& transform = torch::Tensor(),
+                                const std::vector<double>& dist_thres = {0.03}, int64_t sample_nums = 1000000, uint64_t seed = 0);
+    AteResult evalTrajectory();
+
     torch::Device device = torch::kCUDA;
     std::string work_mode = "train";
     InfiniTAM::Engine::CLIEngine* tsdf_engine = nullptr;

@@ -273,6 +273,18 @@ std::pair<torch::Tensor, torch::Tensor> TsdfEngine::MeshScene(int64_t maxTriangl
     return {tri, counts};
 }
 
+GeomEvalResult TsdfEngine::EvalMesh(const torch::Tensor& gt_in, const torch::Tensor& transform, const std::vector<double>& dist_thres,
+                                    int64_t sample_nums, uint64_t seed, int64_t maxTriangles) {
+    TORCH_CHECK(gt_in.defined() && (gt_in.dim() == 2 || gt_in.dim() == 3), "EvalMesh: ground truth must be points [n,3] or triangles [T,3,3]");
+    auto mesh = MeshScene(maxTriangles);
+    const int64_t n = mesh.second.cpu().data_ptr<int64_t>()[0];
+    TORCH_CHECK(n > 0, "EvalMesh: the scene has no triangles");
+    auto rec = mesh.first.slice(0, 0, n).slice(1, 0, 3).reshape({-1, 3}).contiguous();
+    auto gt = gt_in.to(device_);
+    if (gt.dim() == 3) gt = sampleSurface(gt, sample_nums, seed).first;
+    return evalPointClouds(rec, gt.to(torch::kFloat32), transform, dist_thres, sample_nums, seed);
+}
+
 int64_t TsdfEngine::SaveSceneToMesh(const char* fileName, int64_t maxTriangles) {
     auto mesh = MeshScene(maxTriangles);
     const int64_t n = mesh.second.cpu().data_ptr<int64_t>()[0];

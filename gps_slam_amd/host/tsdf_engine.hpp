@@ -20,6 +20,7 @@
 #include <mutex>
 
 #include "gps_host_common.hpp"
+#include "geom_eval.hpp"
 
 enum MemoryDeviceType { MEMORYDEVICE_CPU, MEMORYDEVICE_CUDA };
 
@@ -185,6 +186,13 @@ public:
     int64_t SaveSceneToMesh(const char* fileName, int64_t maxTriangles = (int64_t)1 << 24);
     // {triangles float[maxTriangles,7,3] (p0 p1 p2 c0 c1 c2 clr), counts int64[2]} on the device, no host sync
     std::pair<torch::Tensor, torch::Tensor> MeshScene(int64_t maxTriangles = (int64_t)1 << 24);
+    // Geometric evaluation of the mesh (scripts/geo_general.py on the PLY SaveSceneToMesh writes): MeshScene(), then
+    // evalPointClouds of the cloud the reference's script reads from that PLY -- all 3 * noTotalTriangles vertices, duplicates
+    // included -- against ground-truth points [n,3], or against sample_nums points sampled from ground-truth triangles [T,3,3].
+    // Host-synchronous.
+    GeomEvalResult EvalMesh(const torch::Tensor& gt_points_or_triangles, const torch::Tensor& transform = torch::Tensor(),
+                            const std::vector<double>& dist_thres = {0.03}, int64_t sample_nums = 1000000, uint64_t seed = 0,
+                            int64_t maxTriangles = (int64_t)1 << 24);
     // ITMBasicEngine::SaveToFile / LoadFromFile (ITMBasicEngine.tpp:119-171): <dir>Scene/{voxel.dat, alloc.dat, vba.txt,
     // hash.dat, excess.dat, last.txt} in the reference's MemoryBlockPersister format (size_t count + raw elements)
     void SaveToFile(const std::string& saveOutputDirectory);

@@ -78,6 +78,7 @@ class SLAMPipeline:
         self.curr_cam = None
         self.stats = dict(frames=0, opt_iters=0, raycasts=0, added=0, pruned=0)
         self.workspace_dir, self.saved_mesh, self.saved_engine = ".", "", ""
+        self.gtC2wPoses = []  # dataset pose of every processed frame (ITMBasicEngine::gtC2wPoses), for evalTrajectory
 
     # ------------------------------------------------------------------ slam_pipeline.h:32-49
     def saveMesh(self):
@@ -90,6 +91,25 @@ class SLAMPipeline:
 
     def loadEngine(self):
         self.tsdf.LoadFromFile(self.workspace_dir + "/" + self.saved_engine)
+
+    # ------------------------------------------------------------------ evaluation (scripts/geo_general.py, ate_general.py)
+    def evalGeometry(self, gt_points_or_triangles, **kw):
+        """TsdfEngine.EvalMesh of the attached engine (this pipeline runs its updates inline: nothing to flush)"""
+        if self.tsdf is None:
+            raise RuntimeError("evalGeometry: no TSDF engine attached")
+        return self.tsdf.EvalMesh(gt_points_or_triangles, **kw)
+
+    def evalTrajectory(self):
+        """geom_eval.ate of the engine's stored per-frame poses (camPoses: GetInvM) against the dataset poses of the same frames"""
+        from . import geom_eval
+        if self.tsdf is None:
+            raise RuntimeError("evalTrajectory: no TSDF engine attached")
+        est = [np.asarray(invM, np.float64).reshape(4, 4).T for _, invM in self.tsdf.camPoses]   # ORUtils layout -> row-major
+        if len(est) != len(self.gtC2wPoses):
+            raise ValueError("evalTrajectory: %d stored poses against %d ground-truth poses" % (len(est), len(self.gtC2wPoses)))
+        if len(est) < 3:
+            raise ValueError("evalTrajectory: at least three frames are needed")
+        return geom_eval.ate(np.stack(est), np.stack(self.gtC2wPoses))
 
     # ------------------------------------------------------------------ raycast -> tensors (runRaycastByCam :362-415)
     def runRaycastByCam(self, cam):
@@ -205,6 +225,7 @@ class SLAMPipeline:
             M, invM = self.tsdf.ProcessFrame(rgb_u8_dev, depth_mm_dev, cam.c2w.numpy())
         else:
             M, invM = self.tsdf.ProcessFrameTracked(rgb_u8_dev, depth_mm_dev)
+        self.gtC2wPoses.append(np.asarray(cam.c2w.numpy(), np.float64).copy())
         # est_pose = pose_d->GetInvM() (:81-82): ORUtils layout -> row-major tensor
         cam.c2w_slam = torch.from_numpy(invM.reshape(4, 4).T.copy())
         cam.invalidate()

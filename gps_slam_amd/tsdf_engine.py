@@ -267,6 +267,14 @@ class TsdfEngine:
         tsdf_io.write_mesh_ply(file_name, tri[:n].cpu().numpy())
         return n
 
+    # ---- geometric evaluation of the mesh (scripts/geo_general.py on the PLY SaveSceneToMesh writes): geom_eval.py
+    def EvalMesh(self, gt_points_or_triangles, transform=None, dist_thres=(0.03,), sample_nums=1000000, seed=0,
+                 max_triangles=1 << 24):
+        """MeshScene() + eval_pcd of all its 3 * noTotalTriangles vertices against ground-truth points [n,3] or triangles
+        [T,3,3] -> dict(accuracy_cm, completion_cm, accuracy_ratio[], completion_ratio[], f1[]).  Host-synchronous."""
+        from . import geom_eval
+        return geom_eval.eval_mesh(self, gt_points_or_triangles, transform, dist_thres, sample_nums, seed, max_triangles)
+
     # ---- persistence (ITMBasicEngine::SaveToFile / LoadFromFile, Core/ITMBasicEngine.tpp:119-171): formats in tsdf_io.py
     def SaveToFile(self, save_output_directory):
         import os

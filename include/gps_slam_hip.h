@@ -451,6 +451,29 @@ GPS_API int64_t gps_knn_grid_workspace_bytes(int P);
 GPS_API int gps_knn_mean_dist2_grid(int P, const float *points, float *mean_dist2, void *workspace, int64_t workspace_bytes,
                                     gps_stream stream);
 
+/* ------------------------------------------------------------------ */
+/* Geometry evaluation: exact nearest neighbour between two point sets */
+/* ------------------------------------------------------------------ */
+
+/* The KD-tree query of the reference's reconstruction metrics (scripts/geo_general.py: accuracy, completion and their ratios
+ * between two clouds of ~10^6 points) as device work: an index over the R reference points (the uniform grid of
+ * gps_knn_mean_dist2_grid), then for each of Q query points -- another set, in caller order, anywhere in space -- the squared
+ * distance to the nearest reference point and that point's index.
+ *   dist2[q]    = min over r of |ref[r] - query[q]|^2, computed on the original coordinates (error relative to the distance)
+ *   nn_index[q] = the lowest r that attains it (may be NULL)
+ * Exact, and bit-identical from run to run in both outputs.  A non-finite query gets dist2 = +inf and index -1; non-finite
+ * reference points are nobody's neighbour; a squared distance beyond FLT_MAX counts as +inf.
+ * Work is bounded: the ring search gives up after a fixed number of rings and such queries are finished, as exactly, by a tiled
+ * brute force over all R points in a second launch.  stats (int32[2], may be NULL): queries finished by the grid / by the brute force.
+ * Both workspaces: device memory, 16-byte aligned, no initialisation needed.  The index workspace is only read by
+ * gps_nn_query (several query sets may share it); the query workspace is free for other use between calls.
+ * Q == 0 is a no-op; R == 0 is GPS_ERR_ARG; a workspace that is too small is GPS_ERR_CAPACITY.  No allocation, no host sync. */
+GPS_API int64_t gps_nn_index_workspace_bytes(int R);
+GPS_API int gps_nn_index_build(int R, const float *ref_points, void *ws, int64_t ws_bytes, gps_stream stream);
+GPS_API int64_t gps_nn_query_workspace_bytes(int Q);
+GPS_API int gps_nn_query(int R, const void *index_ws, int Q, const float *query_points, float *dist2, int32_t *nn_index,
+                         int32_t *stats, void *query_ws, int64_t query_ws_bytes, gps_stream stream);
+
 /* The sample mask of SLAMPipeline::initNewGaussians (slam/slam_pipeline.cpp:450-526) in one launch instead of ~12 tensor ops:
  *   valid = depth in (depth_vis_min, depth_vis_max) and vertex.sum(-1) != 0
  *   mask  = mean(|src_rgb - image|, -1) > color_error_thres  and  valid  [and alpha < alpha_vis_max, if alpha != NULL]
