@@ -11,30 +11,12 @@
 // Nothing here uses float atomics: d E is bit-identical run to run.
 #include "common.hpp"
 #include "launch_timing.hpp"
-#include "splat_exposure.hpp"
+#include "splat_compose.hpp"
 
 namespace {
 
 constexpr int EXPO_THREADS = 256;
 constexpr int EXPO_BWD_BLOCKS = GPS_EXPOSURE_BWD_PARTIALS;
-
-// 12 per-thread values -> their workgroup sums in out[0..11] (LDS; valid after the function returns, in every thread): butterfly
-// sums inside each wave, then the four waves in order
-__device__ __forceinline__ void block_sum12(float (&v)[12], float* red /* LDS [4][12] */, float* out /* LDS [12] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 12; k++) v[k] = wave_sum(v[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) red[wave * 12 + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        const int k = threadIdx.x;
-        out[k] = ((red[k] + red[12 + k]) + red[24 + k]) + red[36 + k];
-    }
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(EXPO_THREADS) void compose_exposure_kernel(int P, const float4* __restrict__ render_colors,
                                                                         const float* __restrict__ weight_sum,
@@ -49,17 +31,11 @@ __global__ __launch_bounds__(EXPO_THREADS) void compose_exposure_kernel(int P, c
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += stride) {
         const float4 rc = render_colors[p];
         const float w = weight_sum[p];
-        const float den = w + 1.0f;   // the compose of compose_l1_kernel (splat_optim.hip), operation for operation
-        const float n0 = rc.x + base_color[3 * p], n1 = rc.y + base_color[3 * p + 1], n2 = rc.z + base_color[3 * p + 2];
-        const float c0 = n0 / den, c1 = n1 / den, c2 = n2 / den;
+        const gps::ComposedColor k = gps::compose_color(rc, w, base_color, p);
         float e0, e1, e2;
-        gps::exposure_apply(E, c0, c1, c2, e0, e1, e2);
+        gps::exposure_apply(E, k.c0, k.c1, k.c2, e0, e1, e2);
         rgb[3 * p] = e0; rgb[3 * p + 1] = e1; rgb[3 * p + 2] = e2;
-        if (depth) {
-            const float ref = ref_depth_raw[p];
-            const float bw = ref > 0.f ? 1.f : 0.f;
-            depth[p] = (rc.w + ref * bw) / (w + bw);
-        }
+        if (depth) depth[p] = gps::compose_depth(rc.w, w, ref_depth_raw[p]);
     }
 }
 
@@ -81,7 +57,7 @@ __global__ __launch_bounds__(EXPO_THREADS) void exposure_bwd_kernel(int P, const
                                                                     const float* __restrict__ v_out, float* __restrict__ v_rgb,
                                                                     float* __restrict__ slab, gps::LaunchStamp stamp) {
     gps::StampScope timed(stamp);
-    __shared__ float red[48], tot[12];
+    __shared__ float red[48];
     float E[12], ve[12];
     gps::exposure_load(row, E);
 #pragma unroll
@@ -94,8 +70,8 @@ __global__ __launch_bounds__(EXPO_THREADS) void exposure_bwd_kernel(int P, const
         v_rgb[3 * p] = v0; v_rgb[3 * p + 1] = v1; v_rgb[3 * p + 2] = v2;
         gps::exposure_grad_acc(ve, g0, g1, g2, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2]);
     }
-    block_sum12(ve, red, tot);
-    if (threadIdx.x < 12) slab[(size_t)blockIdx.x * 12 + threadIdx.x] = tot[threadIdx.x];
+    const float tot = gps::block_sum12(ve, red);
+    if (threadIdx.x < 12) slab[(size_t)blockIdx.x * 12 + threadIdx.x] = tot;
 }
 
 // ONE workgroup: thread t sums slab rows t, t + 256, ... (in that order), then block_sum12; grad := the full-table gradient;
@@ -114,7 +90,9 @@ __global__ __launch_bounds__(EXPO_THREADS) void exposure_reduce_kernel(const flo
 #pragma unroll
         for (int k = 0; k < 12; k++) acc[k] += slab[(size_t)s * 12 + k];
     }
-    block_sum12(acc, red, tot);
+    const float sum = gps::block_sum12(acc, red);
+    if (threadIdx.x < 12) tot[threadIdx.x] = sum;
+    __syncthreads();
     const int n = rows * 12;
     for (int e = threadIdx.x; e < n; e += EXPO_THREADS) {
         const int r = e / 12;

@@ -22,7 +22,7 @@
 #include <type_traits>
 
 #include "common.hpp"
-#include "splat_exposure.hpp"
+#include "splat_compose.hpp"
 #include "splat_ssim.hpp"
 
 namespace {
@@ -60,36 +60,20 @@ struct LossArgsExposure : LossArgs {
 template <bool EXPO>
 using Args = std::conditional_t<EXPO, LossArgsExposure, LossArgs>;
 
-__device__ __forceinline__ float composed(const LossArgs& a, int c, int y, int x) {
+// channel c of the composed colour at (y, x), with EXPO of E(composed): what gps_compose_l1 / gps_compose_exposure write there; 0
+// outside the image
+template <bool EXPO>
+__device__ __forceinline__ float composed(const LossArgs& a, [[maybe_unused]] const float (&E)[EXPO ? 12 : 1], int c, int y, int x) {
     if (x >= a.W || y >= a.H || x < 0 || y < 0) return 0.0f;
     const int p = y * a.W + x;
-    const float4 rc = a.render_colors[p];
-    const float den = a.weight_sum[p] + 1.0f;   // the compose of compose_l1_kernel (splat_optim.hip), operation for operation
-    const float n = (c == 0 ? rc.x : (c == 1 ? rc.y : rc.z)) + a.base_color[3 * p + c];
-    return n / den;
-}
-
-// gps::exposure_apply with its multiply-adds spelled out the way the compiler contracts that expression in gps_compose_exposure and
-// gps_exposure_fwd (splat_exposure.hip): left to itself it packs the three rows' products here and contracts them differently,
-// and the stage's rgb has to be the render-only forward's, bit for bit
-__device__ __forceinline__ void exposure_apply_as_composed(const float (&E)[12], float c0, float c1, float c2, float& o0, float& o1,
-                                                           float& o2) {
-    o0 = fmaf(E[2], c2, fmaf(E[0], c0, E[1] * c1)) + E[3];
-    o1 = fmaf(E[6], c2, fmaf(E[4], c0, E[5] * c1)) + E[7];
-    o2 = fmaf(E[10], c2, fmaf(E[8], c0, E[9] * c1)) + E[11];
-}
-
-// channel c of E(composed): gps_compose_exposure's arithmetic (splat_exposure.hip), operation for operation; 0 outside the image
-__device__ __forceinline__ float composed_exposure(const LossArgs& a, const float (&E)[12], int c, int y, int x) {
-    if (x >= a.W || y >= a.H || x < 0 || y < 0) return 0.0f;
-    const int p = y * a.W + x;
-    const float4 rc = a.render_colors[p];
-    const float den = a.weight_sum[p] + 1.0f;
-    const float n0 = rc.x + a.base_color[3 * p], n1 = rc.y + a.base_color[3 * p + 1], n2 = rc.z + a.base_color[3 * p + 2];
-    const float c0 = n0 / den, c1 = n1 / den, c2 = n2 / den;
-    float e0, e1, e2;
-    exposure_apply_as_composed(E, c0, c1, c2, e0, e1, e2);
-    return c == 0 ? e0 : (c == 1 ? e1 : e2);
+    if constexpr (EXPO) {
+        const gps::ComposedColor k = gps::compose_color(a.render_colors[p], a.weight_sum[p], a.base_color, p);
+        float e0, e1, e2;
+        gps::exposure_apply(E, k.c0, k.c1, k.c2, e0, e1, e2);
+        return c == 0 ? e0 : (c == 1 ? e1 : e2);
+    } else {
+        return gps::compose_channel(a.render_colors[p], a.weight_sum[p], a.base_color, p, c);
+    }
 }
 
 __device__ __forceinline__ float image_at(const float* __restrict__ img, int c, int y, int x, int H, int W) {
@@ -111,20 +95,6 @@ __device__ __forceinline__ void block_sum4(float (&v)[SLAB_ROW], float* red /* L
         v[k] = ((red[k] + red[SLAB_ROW + k]) + red[2 * SLAB_ROW + k]) + red[3 * SLAB_ROW + k];
 }
 
-// 12 per-thread values -> workgroup sum k returned in thread k < 12: butterfly sums inside each wave, then the four waves in order
-__device__ __forceinline__ float block_sum12(float (&v)[12], float* red /* LDS [4][12] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 12; k++) v[k] = wave_sum(v[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) red[wave * 12 + k] = v[k];
-    }
-    __syncthreads();
-    const int k = threadIdx.x < 12 ? threadIdx.x : 0;
-    return ((red[k] + red[12 + k]) + red[24 + k]) + red[36 + k];
-}
-
 template <bool SSIM, bool EXPO = false>
 __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(Args<EXPO> a) {
     __shared__ float ta[SSIM ? TIN : 1][LD_IN], tb[SSIM ? TIN : 1][LD_IN];
@@ -138,8 +108,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(Args<EXPO> a) {
     if constexpr (SSIM) {
         for (int q = tid; q < TIN * TIN; q += LOSS_THREADS) {
             const int ly = q / TIN, lx = q - ly * TIN;
-            if constexpr (EXPO) ta[ly][lx] = composed_exposure(a, E, c, y0 + ly - HALO, x0 + lx - HALO);
-            else ta[ly][lx] = composed(a, c, y0 + ly - HALO, x0 + lx - HALO);
+            ta[ly][lx] = composed<EXPO>(a, E, c, y0 + ly - HALO, x0 + lx - HALO);
             tb[ly][lx] = image_at(a.gt_rgb, c, y0 + ly - HALO, x0 + lx - HALO, H, W);
         }
         __syncthreads();
@@ -160,8 +129,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(Args<EXPO> a) {
         const int p = y * W + x;
         float col;
         if constexpr (SSIM) col = ta[ly + HALO][lx + HALO];
-        else if constexpr (EXPO) col = composed_exposure(a, E, c, y, x);
-        else col = composed(a, c, y, x);
+        else col = composed<EXPO>(a, E, c, y, x);
         a.rgb[3 * p + c] = col;
         acc[0] += fabsf(a.gt_rgb[3 * p + c] - col);
         if constexpr (SSIM) {
@@ -172,10 +140,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(Args<EXPO> a) {
             a.maps[3 * P + o] = d_sigma1_sq(pt);
             a.maps[6 * P + o] = d_sigma12(pt);
         }
-        if (c == 0 && a.depth) {   // depth = (raw_d + ref [ref > 0]) / (W + [ref > 0]) (raw_gs_model.cpp:324-326)
+        if (c == 0 && a.depth) {
             const float ref = a.ref_depth_raw[p];
-            const float bw = ref > 0.f ? 1.f : 0.f;
-            const float d = (a.render_colors[p].w + ref * bw) / (a.weight_sum[p] + bw);
+            const float d = gps::compose_depth(a.render_colors[p].w, a.weight_sum[p], ref);
             a.depth[p] = d;
             if (a.gt_depth) {
                 const float gd = a.gt_depth[p];
@@ -271,7 +238,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(Args<EXPO> a) {
             const int p = y * W + x;
             const float col = a.rgb[3 * p + c], gt = a.gt_rgb[3 * p + c];
             const float d = gt - col;
-            float gc = d > 0.f ? -g_l1 : (d < 0.f ? g_l1 : 0.f);   // sgn(0) = 0 as in torch
+            float gc = gps::l1_sign_grad(d, g_l1);
             if constexpr (SSIM) gc += ypass3(h, ly, lx, col, gt);
             g[j][c] = gc;
         }
@@ -291,37 +258,28 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(Args<EXPO> a) {
         const int p = y * W + x;
         const float4 rc = a.render_colors[p];
         const float w = a.weight_sum[p];
-        const float den = w + 1.0f;
-        const float n0 = rc.x + a.base_color[3 * p], n1 = rc.y + a.base_color[3 * p + 1], n2 = rc.z + a.base_color[3 * p + 2];
-        const float dd = den * den;
+        const gps::ComposedColor k = gps::compose_color(rc, w, a.base_color, p);
         if constexpr (EXPO) {   // g: d loss / d E(lin) -> d loss / d E, then d loss / d lin
-            gps::exposure_grad_acc(ve, g[j][0], g[j][1], g[j][2], n0 / den, n1 / den, n2 / den);
+            gps::exposure_grad_acc(ve, g[j][0], g[j][1], g[j][2], k.c0, k.c1, k.c2);
             float v0, v1, v2;
             gps::exposure_vjp(E, g[j][0], g[j][1], g[j][2], v0, v1, v2);
             g[j][0] = v0; g[j][1] = v1; g[j][2] = v2;
         }
-        float va = -(g[j][0] * n0) / dd - (g[j][1] * n1) / dd - (g[j][2] * n2) / dd;
-        float v3 = 0.f;
+        float v0, v1, v2, va, v3 = 0.f;
+        gps::compose_color_bwd(k, g[j][0], g[j][1], g[j][2], v0, v1, v2, va);
         if (g_depth > 0.f) {
             const float gd = a.gt_depth[p], dep = a.depth[p];
-            if (gd > 0.f && dep > 0.f) {   // (valid: the denominator W + [ref > 0] is positive here)
-                const float ref = a.ref_depth_raw[p];
-                const float bw = ref > 0.f ? 1.f : 0.f;
-                const float dden = w + bw, nd = rc.w + ref * bw;
-                const float e = gd - dep;
-                const float gz = e > 0.f ? -g_depth : (e < 0.f ? g_depth : 0.f);
-                v3 = gz / dden;
-                va -= (gz * nd) / (dden * dden);
-            }
+            if (gd > 0.f && dep > 0.f)   // (valid: the denominator W + [ref > 0] is positive here)
+                gps::compose_depth_bwd(rc.w, w, a.ref_depth_raw[p], gps::l1_sign_grad(gd - dep, g_depth), v3, va);
         }
-        a.v_render_colors[p] = make_float4(g[j][0] / den, g[j][1] / den, g[j][2] / den, v3);
+        a.v_render_colors[p] = make_float4(v0, v1, v2, v3);
         a.v_render_alphas[p] = va;
         // what the strip backward gathers per pixel: {d loss / d weight sum, the depth cut ref_depth + delta_depth}
         if (a.pix2) a.pix2[p] = make_float2(va, a.ref_depth_clamped[p] + a.delta_depth);
     }
     if constexpr (EXPO) {   // this tile's row of the exposure slab (every launched tile holds a pixel)
         __syncthreads();    // dred is consumed: its memory holds the four waves' sums
-        const float tot = block_sum12(ve, reinterpret_cast<float*>(&dred[0][0]));
+        const float tot = gps::block_sum12(ve, reinterpret_cast<float*>(&dred[0][0]));
         if (tid < 12) a.eslab[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 12 + tid] = tot;
     }
 }

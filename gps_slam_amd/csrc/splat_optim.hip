@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "splat_adam.hpp"
+#include "splat_compose.hpp"
 
 namespace {
 
@@ -27,26 +28,19 @@ __global__ __launch_bounds__(256) void compose_l1_kernel(int P, const float4* __
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += stride) {
         const float4 rc = render_colors[p];
         const float w = weight_sum[p];
-        const float den = w + 1.0f;  // base colour weight is always 1 (raw_gs_model.cpp:321-323)
-        const float n0 = rc.x + base_color[3 * p], n1 = rc.y + base_color[3 * p + 1], n2 = rc.z + base_color[3 * p + 2];
-        const float c0 = n0 / den, c1 = n1 / den, c2 = n2 / den;
-        rgb[3 * p] = c0; rgb[3 * p + 1] = c1; rgb[3 * p + 2] = c2;
-        if (depth) {
-            const float ref = ref_depth_raw[p];
-            const float bw = ref > 0.f ? 1.f : 0.f;  // depth weight only where the raycast hit (:324-326)
-            depth[p] = (rc.w + ref * bw) / (w + bw);
-        }
+        const gps::ComposedColor k = gps::compose_color(rc, w, base_color, p);
+        rgb[3 * p] = k.c0; rgb[3 * p + 1] = k.c1; rgb[3 * p + 2] = k.c2;
+        if (depth) depth[p] = gps::compose_depth(rc.w, w, ref_depth_raw[p]);
         if (gt_rgb == nullptr) continue;  // render-only call (NoGradGuard paths of the reference)
-        const float d0 = gt_rgb[3 * p] - c0, d1 = gt_rgb[3 * p + 1] - c1, d2 = gt_rgb[3 * p + 2] - c2;
+        const float d0 = gt_rgb[3 * p] - k.c0, d1 = gt_rgb[3 * p + 1] - k.c1, d2 = gt_rgb[3 * p + 2] - k.c2;
         part += fabsf(d0) + fabsf(d1) + fabsf(d2);
         if (v_render_colors) {
-            // d mean|gt - rgb| / d rgb = -sgn(gt - rgb) / (3P); sgn(0) = 0 as in torch
-            const float g0 = d0 > 0.f ? -inv_count : (d0 < 0.f ? inv_count : 0.f);
-            const float g1 = d1 > 0.f ? -inv_count : (d1 < 0.f ? inv_count : 0.f);
-            const float g2 = d2 > 0.f ? -inv_count : (d2 < 0.f ? inv_count : 0.f);
-            v_render_colors[p] = make_float4(g0 / den, g1 / den, g2 / den, 0.f);
-            const float dd = den * den;
-            v_render_alphas[p] = -(g0 * n0) / dd - (g1 * n1) / dd - (g2 * n2) / dd;
+            // d mean|gt - rgb| / d rgb = -sgn(gt - rgb) / (3P)
+            float v0, v1, v2, va;
+            gps::compose_color_bwd(k, gps::l1_sign_grad(d0, inv_count), gps::l1_sign_grad(d1, inv_count),
+                                   gps::l1_sign_grad(d2, inv_count), v0, v1, v2, va);
+            v_render_colors[p] = make_float4(v0, v1, v2, 0.f);
+            v_render_alphas[p] = va;
         }
     }
     part = wave_sum(part);

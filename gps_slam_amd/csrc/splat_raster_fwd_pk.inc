@@ -150,16 +150,17 @@ __global__ __launch_bounds__(FWD_THREADS) void GPS_FWD_PK_NAME(
         if (in0) { render_colors[pix] = c0; render_alphas[pix] = w0; }
         if (in1) { render_colors[pix + 1] = c1; render_alphas[pix + 1] = w1; }
         if (fc.base_color) {
-            // compose + L1 + image gradients of the two pixels, operation for operation what compose_l1_kernel does
+            // compose + L1 + image gradients of the two pixels
             float lsum = 0.f;
 #if GPS_FWD_PK_EXPOSURE
             float E[12];
             gps::exposure_load(ex.row, E);
-            if (in0) lsum += compose_l1_pixel_exposure(fc, E, ve, pix, c0, w0, cut0);
-            if (in1) lsum += compose_l1_pixel_exposure(fc, E, ve, pix + 1, c1, w1, cut1);
+            if (in0) lsum += compose_l1_pixel<true>(fc, E, ve, pix, c0, w0, cut0);
+            if (in1) lsum += compose_l1_pixel<true>(fc, E, ve, pix + 1, c1, w1, cut1);
 #else
-            if (in0) lsum += compose_l1_pixel(fc, pix, c0, w0, cut0);
-            if (in1) lsum += compose_l1_pixel(fc, pix + 1, c1, w1, cut1);
+            float none[1];
+            if (in0) lsum += compose_l1_pixel<false>(fc, none, none, pix, c0, w0, cut0);
+            if (in1) lsum += compose_l1_pixel<false>(fc, none, none, pix + 1, c1, w1, cut1);
 #endif
             lsum = wave_sum(lsum);
             if (lane == 0) atomicAdd(fc.loss, lsum * fc.inv_count);

@@ -509,13 +509,11 @@ def test_record_streaming_forward_equals_lds_forward(N, W, H):
 
 
 @pytest.mark.parametrize("N,W,H", [(150000, 640, 480), (300000, 1200, 680), (4000, 50, 37), (1, 33, 17), (30000, 1600, 720), (600, 2560, 1440)])
-def test_persistent_forward_is_bit_identical_to_the_per_tile_forward(N, W, H):
-    """raster_ges_fwd_pp_kernel (persistent workgroups, snake-dealt tiles, records staged one item ahead) against
-    raster_ges_fwd_pk_kernel (one workgroup per tile): the same staging arithmetic, culling, survivor partition and summation order,
-    so the render and the weight sum must be IDENTICAL bit for bit -- row-major tile order and a permuted tile_order (the dealing
-    changes which workgroup renders a tile, never what it computes).  Sizes: BASELINE's 640x480, Replica's 1200x680 (ragged last
-    tile row), tiny images (fewer tiles than workgroups: the launcher keeps the per-tile kernel), 1600x720 and a 1440p image whose
-    14,400 tiles are 19 passes per workgroup, many of them with an empty list."""
+def test_per_tile_forward_with_a_permuted_tile_order_is_bit_identical_to_row_major(N, W, H):
+    """raster_ges_fwd_pk_kernel (one workgroup per tile) launched with a permuted tile_order against the row-major launch: the order
+    changes which workgroup renders a tile, never what it computes, so the render and the weight sum must be IDENTICAL bit for bit.
+    Sizes: BASELINE's 640x480, Replica's 1200x680 (ragged last tile row), tiny images (fewer tiles than the chip has workgroup
+    slots), 1600x720 and a 1440p image with 14,400 tiles, many of them with an empty list."""
     from gps_slam_amd import gsplat_ops as ops
     from gps_slam_amd._lib import check, lib
     import ctypes as C
@@ -536,8 +534,7 @@ def test_persistent_forward_is_bit_identical_to_the_per_tile_forward(N, W, H):
     ptr = lambda t: C.c_void_p(t.data_ptr())
     sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def render(persistent, tile_order):
-        lib.gps_set_raster_fwd_persistent(1 if persistent else 0)
+    def render(tile_order):
         rc = torch.full((1, H, W, 4), float("nan"), device=_dev())
         ra = torch.full((1, H, W, 1), float("nan"), device=_dev())
         check(lib.gps_raster_ges_fwd_rec_ordered(N, ptr(rec), ptr(tref), W, H, ptr(isect.isect_offsets), ptr(isect.flatten_ids), ptr(isect.counts),
@@ -545,14 +542,10 @@ def test_persistent_forward_is_bit_identical_to_the_per_tile_forward(N, W, H):
               "gps_raster_ges_fwd_rec_ordered")
         torch.cuda.synchronize()
         return rc, ra
-    try:
-        rc0, ra0 = render(False, None)
-        assert torch.isfinite(rc0).all() and torch.isfinite(ra0).all()
-        for tile_order in (None, order):
-            rc1, ra1 = render(True, tile_order)
-            assert torch.equal(rc1, rc0) and torch.equal(ra1, ra0), "persistent forward differs (tile_order %s)" % ("given" if tile_order is not None else "row-major")
-    finally:
-        lib.gps_set_raster_fwd_persistent(0)   # (the shipped default)
+    rc0, ra0 = render(None)
+    assert torch.isfinite(rc0).all() and torch.isfinite(ra0).all()
+    rc1, ra1 = render(order)
+    assert torch.equal(rc1, rc0) and torch.equal(ra1, ra0), "the forward with a permuted tile_order differs from the row-major one"
 
 
 def test_adam_step_one_writes_the_moments_without_reading_them():
