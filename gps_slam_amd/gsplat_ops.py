@@ -241,6 +241,45 @@ def rasterize_to_pixels_bwd_ges_gs_parallel(means2d, conics, colors, opacities, 
     return v_m, v_c, v_col, v_o
 
 
+def raster_pack_records(means2d, conics, colors, opacities, radii):
+    """gps_raster_pack_records: the 48-byte records of gps_gauss_preprocess_fwd from the operator-level arrays -> recs[max(N,1),12]"""
+    means2d, conics, colors, opacities = _f32c(means2d), _f32c(conics), _f32c(colors), _f32c(opacities)
+    radii = radii.contiguous().view(-1)
+    N, dev = opacities.numel(), means2d.device
+    recs = torch.empty((max(N, 1), 12), dtype=torch.float32, device=dev)
+    check(lib.gps_raster_pack_records(N, _ptr(means2d), _ptr(conics), _ptr(colors), _ptr(opacities), _ptr(radii), _ptr(recs), _stream()),
+          "gps_raster_pack_records")
+    return recs
+
+
+def raster_pair_image(v_render_alphas, ref_depth_map, width, height, delta_depth):
+    """gps_raster_pair_image: {d loss / d weight sum, ref_depth + delta_depth} per pixel -> pix2[H*W,2]"""
+    v_render_alphas, ref_depth_map = _f32c(v_render_alphas), _f32c(ref_depth_map)
+    pix2 = torch.empty((height * width, 2), dtype=torch.float32, device=v_render_alphas.device)
+    check(lib.gps_raster_pair_image(width, height, _ptr(v_render_alphas), _ptr(ref_depth_map), delta_depth, _ptr(pix2), _stream()),
+          "gps_raster_pair_image")
+    return pix2
+
+
+def raster_ges_bwd_strips_lists(recs, radii, cls_ids, cls_counts, v_render_colors, pix2, width, height, rows):
+    """gps_raster_ges_bwd_strips on caller-made class lists: recs[N,12], radii[N] i32, cls_ids[5,stride] i32 (row k: the ids of
+    class k, any order), cls_counts[>=5] i32 (device), v_render_colors[..,H,W,4], pix2[H*W,2], rows[N,12] (caller-owned).
+    The kernel stores the row of every listed id {v_colors[4], v_conics[3], v_means2d[2], v_opacity, 0, 0} and touches no
+    other row: nothing is zero-filled here.  -> rows"""
+    assert recs.dtype == torch.float32 and recs.is_contiguous() and rows.dtype == torch.float32 and rows.is_contiguous()
+    assert radii.dtype == torch.int32 and radii.is_contiguous()
+    assert cls_ids.dtype == torch.int32 and cls_ids.is_contiguous() and cls_ids.dim() == 2 and cls_ids.shape[0] == 5
+    assert cls_counts.dtype == torch.int32 and cls_counts.is_contiguous() and cls_counts.numel() >= 5
+    assert pix2.dtype == torch.float32 and pix2.is_contiguous() and pix2.numel() == 2 * width * height
+    v_render_colors = _f32c(v_render_colors)
+    assert v_render_colors.numel() == 4 * width * height
+    N = radii.numel()
+    assert recs.shape[0] >= N and rows.shape[0] >= N and recs.shape[1] == 12 and rows.shape[1] == 12
+    check(lib.gps_raster_ges_bwd_strips(N, _ptr(recs), _ptr(radii), _ptr(cls_ids), _ptr(cls_counts), cls_ids.shape[1], _ptr(v_render_colors),
+                                        _ptr(pix2), width, height, _ptr(rows), _stream()), "gps_raster_ges_bwd_strips")
+    return rows
+
+
 def rasterize_to_pixels_bwd_ges_strips(means2d, conics, colors, opacities, radii, ref_depth_map, width, height, delta_depth,
                                        v_render_colors, v_render_alphas):
     """The same operator through the kernel the fused train step runs (gps_raster_ges_bwd_strips: column strips, one 48-byte
@@ -248,15 +287,10 @@ def rasterize_to_pixels_bwd_ges_strips(means2d, conics, colors, opacities, radii
     from the operator-level arrays (the train step's binning writes them on the device; this wrapper, used by the parity tests,
     orders the lists with torch).  Same outputs as rasterize_to_pixels_bwd_ges_gs_parallel; untouched rows are zero."""
     means2d, conics, colors, opacities = _f32c(means2d), _f32c(conics), _f32c(colors), _f32c(opacities)
-    ref_depth_map, v_render_colors, v_render_alphas = _f32c(ref_depth_map), _f32c(v_render_colors), _f32c(v_render_alphas)
     radii = radii.contiguous().view(-1)
     N, dev = opacities.numel(), means2d.device
-    recs = torch.empty((max(N, 1), 12), dtype=torch.float32, device=dev)
-    check(lib.gps_raster_pack_records(N, _ptr(means2d), _ptr(conics), _ptr(colors), _ptr(opacities), _ptr(radii), _ptr(recs), _stream()),
-          "gps_raster_pack_records")
-    pix2 = torch.empty((height * width, 2), dtype=torch.float32, device=dev)
-    check(lib.gps_raster_pair_image(width, height, _ptr(v_render_alphas), _ptr(ref_depth_map), delta_depth, _ptr(pix2), _stream()),
-          "gps_raster_pair_image")
+    recs = raster_pack_records(means2d, conics, colors, opacities, radii)
+    pix2 = raster_pair_image(v_render_alphas, ref_depth_map, width, height, delta_depth)
     cls = torch.full((N,), -1, dtype=torch.long, device=dev)
     vis = radii > 0
     cls[vis] = torch.bucketize(radii[vis].long(), torch.tensor([4, 8, 16, 32], device=dev), right=False)
@@ -267,9 +301,7 @@ def rasterize_to_pixels_bwd_ges_strips(means2d, conics, colors, opacities, radii
         ids[k, :sel.numel()] = sel
         counts[k] = sel.numel()
     rows = torch.zeros((max(N, 1), 12), dtype=torch.float32, device=dev)
-    check(lib.gps_raster_ges_bwd_strips(N, _ptr(recs), _ptr(radii), _ptr(ids), _ptr(counts), max(N, 1), _ptr(v_render_colors), _ptr(pix2),
-                                        width, height, _ptr(rows), _stream()), "gps_raster_ges_bwd_strips")
-    rows = rows[:N]
+    rows = raster_ges_bwd_strips_lists(recs, radii, ids, counts, v_render_colors, pix2, width, height, rows)[:N]
     return (rows[:, 7:9].reshape(means2d.shape).contiguous(), rows[:, 4:7].reshape(conics.shape).contiguous(),
             rows[:, 0:4].reshape(colors.shape).contiguous(), rows[:, 9].reshape(opacities.shape).contiguous())
 
