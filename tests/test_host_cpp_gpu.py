@@ -35,9 +35,9 @@ def _scene(N=20000, W=320, H=240, seed=3):
     return tensors, c2w, K, gt, base, ref
 
 
-def _cpp_model(h, tensors, lr0=False):
+def _cpp_model(h, tensors, lr0=False, **extra):
     m = h.SLAMGaussianModel()
-    cfg = dict(capacity=1 << 16)
+    cfg = dict(capacity=1 << 16, **extra)
     if lr0:
         cfg.update({k: 0.0 for k in ("means_lr", "scales_lr", "quats_lr", "featuresDc_lr", "featuresRest_lr", "opacities_lr")})
     m.loadConfig(cfg)
@@ -181,11 +181,80 @@ def test_raw_render_method_cpp_host_matches_python_mirror_and_trains():
     assert losses[-1] < 0.95 * losses[0] and all(b < a for a, b in zip(losses, losses[1:])), losses
 
 
+def _wide_scene(W=96, H=64):
+    """_scene under scenes.wide_camera: fx != fy, principal point off the centre, a pose rotated about all three axes -- an exchange
+    of two of them on the way from Camera to the kernels' K / viewmat / cam_pos changes the render"""
+    from tests import wide_cases as wc
+    case = wc.wide_case(W, H)
+    g = case.g
+    gen = torch.Generator().manual_seed(3)
+    gt = torch.rand((H, W, 3), generator=gen).to(DEV)
+    base = torch.rand((H, W, 3), generator=gen).to(DEV)
+    ref = (torch.rand((H, W, 1), generator=gen) * 4).to(DEV)
+    ref[ref < 0.4] = 0.0
+    tensors = [T(g["means"]), T(g["log_scales"]), T(g["quats"]), T(g["sh"][:, 0].copy()), T(g["sh"][:, 1:].copy()), T(g["opac_logit"])]
+    return tensors, case.c2w, case.K, gt, base, ref
+
+
 def test_cpp_model_matches_python_model_and_autograd_route_matches_fused():
+    h, tensors, ccam, ref, base = _cpp_model_against_python_model(320, 240, _scene())
+    _autograd_route_against_fused(h, tensors, ccam, ref, base)
+
+
+def test_cpp_model_matches_python_model_under_the_wide_camera():
+    """The same under scenes.wide_camera (96x64, the 4000 Gaussians of scenes.wide_gaussians).  A Camera -> K / viewmat / cam_pos
+    that exchanges fx with fy, cx with cy or transposes the pose on one host shows here and nowhere under the default camera.
+    The autograd half leaves out the elements whose gradient is below 1e-5 of its row's largest (see the helper): on this scene
+    d loss / d log_scales[3020, 1] is 7.98e-14 from the group backward and 9.49e-14 from the strip backward at step 2, 3e-6 of that
+    row's largest element (2.63e-8), and Adam turns those 16 % of a rounding residue into 0.12 lr = 6.2e-4 (LABBOOK section 22)."""
+    h, tensors, ccam, ref, base = _cpp_model_against_python_model(96, 64, _wide_scene(96, 64))
+    _autograd_route_against_fused(h, tensors, ccam, ref, base, leave_out_cancelled=True)
+
+
+def _autograd_route_against_fused(h, tensors, ccam, ref, base, leave_out_cancelled=False):
+    """reference call sequence on a fresh C++ model == fused trainStep on another.
+    leave_out_cancelled: Adam divides every element by its own magnitude, so the bound below presumes that an element's gradient
+    is known to a relative 1e-3.  An element below 1e-5 of the largest gradient of its row (its Gaussian, within one tensor) is not:
+    it is what is left of that row's terms after they cancel, and those carry the rasterizer sums' rounding, 2e-5 of the sum of
+    |terms| by this project's own allowance.  Such elements (by the fused route's gradient at either step) are left out, and there
+    may be at most 1 % of them, so that the exemption cannot become the test."""
+    # (Adam mode 0 where the gradients are read: the same kernels with the gradients written out; modes 0 and 2 end bit-equal)
+    a_model = _cpp_model(h, tensors)
+    f_model = _cpp_model(h, tensors, fuse_sh_rest_adam=0.0) if leave_out_cancelled else _cpp_model(h, tensors)
+    a_model.initOptimizers(-1, 3.3)
+    f_model.initOptimizers(-1, 3.3)
+    keep = None
+    for _ in range(2):
+        res = a_model.forward(ccam, ref, base)
+        loss = a_model.computeLoss(res, ccam, dict(l1_weight=1.0))
+        loss["loss"].backward()
+        a_model.optimizersStep()
+        a_model.optimizersZeroGrad()
+        f_model.trainStep(ccam, ref, base)
+        if leave_out_cancelled:
+            known = []
+            for g in f_model.grads():
+                g2 = g.reshape(g.shape[0], -1).abs()
+                known.append((g2 >= 1e-5 * g2.max(1, keepdim=True).values).reshape(g.shape))
+            keep = known if keep is None else [x & y for x, y in zip(keep, known)]
+    torch.cuda.synchronize()
+    ap, fp = a_model.getGaussianParms(), f_model.getGaussianParms()
+    for k, name in enumerate(("getMeans", "getScales", "getQuats", "getFeaturesDc", "getFeaturesRest", "getOpacities")):
+        a, b = getattr(ap, name)(), getattr(fp, name)()
+        if keep is not None:
+            left_out = int((~keep[k]).sum())
+            print("%s: %d of %d elements left out (gradient below 1e-5 of its row)" % (name, left_out, keep[k].numel()))
+            assert left_out <= 0.01 * keep[k].numel(), (name, left_out)
+            a, b = a[keep[k]], b[keep[k]]
+        # Adam normalises the step, so gradient rounding differences (atomics order, compose in torch vs fused) show up
+        # at the 1e-3 * lr level at most
+        torch.testing.assert_close(a, b, rtol=1e-3, atol=2e-4)
+
+
+def _cpp_model_against_python_model(W, H, scene):
     h = _host()
     from gps_slam_amd.gs_model import Camera, SLAMGaussianModel
-    W, H = 320, 240
-    tensors, c2w, K, gt, base, ref = _scene()
+    tensors, c2w, K, gt, base, ref = scene
     # python model
     pm = SLAMGaussianModel(device=DEV)
     pm.add_params(dict(zip(("means", "scales", "quats", "featuresDc", "featuresRest", "opacities"), [t.clone() for t in tensors])))
@@ -210,25 +279,7 @@ def test_cpp_model_matches_python_model_and_autograd_route_matches_fused():
     got = [cp.getMeans(), cp.getScales(), cp.getQuats(), cp.getFeaturesDc(), cp.getFeaturesRest(), cp.getOpacities()]
     for a, b in zip(got, pm.opt_gs_params.tensors()):
         torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5)
-
-    # reference call sequence on a fresh C++ model == fused trainStep on another
-    a_model, f_model = _cpp_model(h, tensors), _cpp_model(h, tensors)
-    a_model.initOptimizers(-1, 3.3)
-    f_model.initOptimizers(-1, 3.3)
-    for _ in range(2):
-        res = a_model.forward(ccam, ref, base)
-        loss = a_model.computeLoss(res, ccam, dict(l1_weight=1.0))
-        loss["loss"].backward()
-        a_model.optimizersStep()
-        a_model.optimizersZeroGrad()
-        f_model.trainStep(ccam, ref, base)
-    torch.cuda.synchronize()
-    ap, fp = a_model.getGaussianParms(), f_model.getGaussianParms()
-    for name in ("getMeans", "getScales", "getQuats", "getFeaturesDc", "getFeaturesRest", "getOpacities"):
-        a, b = getattr(ap, name)(), getattr(fp, name)()
-        # Adam normalises the step, so gradient rounding differences (atomics order, compose in torch vs fused) show up
-        # at the 1e-3 * lr level at most
-        torch.testing.assert_close(a, b, rtol=1e-3, atol=2e-4)
+    return h, tensors, ccam, ref, base
 
 
 def test_cpp_train_step_run_ahead_equals_plain_steps_and_is_void_after_prune_or_new_pose():

@@ -13,43 +13,11 @@ import torch
 
 from oracle import splat_ref as orc
 from tests import scenes
+from tests.wide_cases import torch_project as _torch_project
 
 torch.manual_seed(0)
 W, H, TS = 96, 64, 16
 TW, TH = (W + TS - 1) // TS, (H + TS - 1) // TS
-
-
-def _torch_project(means, quats, scales, viewmat, K, W, H, eps2d=0.3):
-    """Dense float64 restatement of the pinhole projection maths (for autograd)."""
-    R, t = viewmat[:3, :3], viewmat[:3, 3]
-    mc = means @ R.T + t
-    q = quats / quats.norm(dim=1, keepdim=True)
-    w, x, y, z = q.unbind(1)
-    Rq = torch.stack([
-        1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
-    M = Rq * scales[:, None, :]
-    cov = M @ M.transpose(1, 2)
-    cov_c = R @ cov @ R.T
-    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
-    X, Y, Z = mc.unbind(1)
-    tfx, tfy = 0.5 * W / fx, 0.5 * H / fy
-    lxp, lxn = (W - cx) / fx + 0.3 * tfx, cx / fx + 0.3 * tfx
-    lyp, lyn = (H - cy) / fy + 0.3 * tfy, cy / fy + 0.3 * tfy
-    rz = 1 / Z
-    tx = Z * torch.minimum(lxp, torch.maximum(-lxn, X * rz))
-    ty = Z * torch.minimum(lyp, torch.maximum(-lyn, Y * rz))
-    zero = torch.zeros_like(Z)
-    J = torch.stack([fx * rz, zero, -fx * tx * rz * rz, zero, fy * rz, -fy * ty * rz * rz], 1).reshape(-1, 2, 3)
-    c2 = J @ cov_c @ J.transpose(1, 2)
-    c2 = c2 + eps2d * torch.eye(2, dtype=c2.dtype)
-    det = c2[:, 0, 0] * c2[:, 1, 1] - c2[:, 0, 1] * c2[:, 1, 0]
-    conic = torch.stack([c2[:, 1, 1] / det, -c2[:, 0, 1] / det, c2[:, 0, 0] / det], 1)
-    m2 = torch.stack([fx * X * rz + cx, fy * Y * rz + cy], 1)
-    b = 0.5 * (c2[:, 0, 0] + c2[:, 1, 1])
-    radius = torch.ceil(3 * torch.sqrt(b + torch.sqrt(torch.clamp(b * b - det, min=0.01))))
-    return m2, Z, conic, radius, det
 
 
 def _scene(N=400, seed=3):
@@ -448,3 +416,82 @@ def test_ssim_restatement_matches_the_reference_kernels_outputs():
         g = orc.ssim_bwd(img1, img2, dL, z[tag + "_dm_dmu1"], z[tag + "_dm_dsigma1_sq"], z[tag + "_dm_dsigma12"])
         want = z[tag + "_grad"]
         np.testing.assert_allclose(g, want, rtol=1e-3, atol=1e-4 * np.abs(want).max(), err_msg=tag + "grad")
+
+
+# ----------------------------------------------------------------------------- the wide camera: fov clamp arms, cull planes, radius_clip
+def _wide_sizes():
+    from tests import wide_cases
+    return wide_cases.SIZES
+
+
+@pytest.mark.parametrize("Ww,Hw", _wide_sizes())
+def test_wide_projection_forward_matches_dense_torch(Ww, Hw):
+    """fx != fy, off-centre principal point, rotated pose, Gaussians beyond all four clamp limits, behind the camera and around
+    the near plane (tests/scenes.py: wide_gaussians): values, radii and the cull set against float64."""
+    from tests import wide_cases as wc
+    case = wc.wide_case(Ww, Hw)
+    _, (tm2, tz, tconic, tr, tdet) = wc.torch_project64(case)
+    tm2, tz, tconic, tr, tdet = (a.numpy() for a in (tm2, tz, tconic, tr, tdet))
+    vis = case.r0 > 0
+    np.testing.assert_allclose(case.m0[vis], tm2[vis], rtol=1e-4, atol=1e-3)
+    np.testing.assert_allclose(case.d0[vis], tz[vis], rtol=1e-5)
+    np.testing.assert_allclose(case.c0[vis], tconic[vis], rtol=2e-3, atol=1e-5)
+    print("wide %dx%d: conic relative error max %.2e" % (Ww, Hw, (np.abs(case.c0[vis] - tconic[vis]).max(1) / np.abs(tconic[vis]).max(1)).max()))
+    assert (case.r0[vis] == tr[vis]).all()
+    decided = ~case.cls["on_near"]
+    culled = wc.cull64(tm2, tz, tr, tdet, Ww, Hw)
+    assert ((case.r0 == 0) == culled)[decided].all(), int((((case.r0 == 0) != culled) & decided).sum())
+    assert (case.r0[case.cls["behind"] & decided] == 0).all()
+
+
+@pytest.mark.parametrize("Ww,Hw", _wide_sizes())
+def test_wide_projection_backward_matches_autograd(Ww, Hw):
+    """Both arms of both clamps (the `else` arms route vJ02 / vJ12 into v_z) against float64 autograd of the same loss."""
+    from tests import wide_cases as wc
+    b = wc.wide_bwd_case(Ww, Hw)
+    cmp_ = b.cmp
+    for got, ref, name in zip(b.e, b.ref64, ("v_means", "v_quats", "v_scales")):
+        scale = np.abs(ref[cmp_]).max()
+        row = np.abs(got[cmp_] - ref[cmp_]).max(1) / np.abs(ref[cmp_]).max(1)
+        print("wide %dx%d %s: per-row relative error max %.2e" % (Ww, Hw, name, row.max()))
+        np.testing.assert_allclose(got[cmp_], ref[cmp_], rtol=5e-3, atol=2e-4 * scale, err_msg=name)
+        assert (got[~b.vis] == 0).all(), name
+    # EVERY row within its own condition budget (scenes.condition_budget: what 1-ulp jitter of the float32 inputs does to that row,
+    # times 32, plus 2e-5 of the row): the tolerance above is relative to the largest gradient of the scene, and a term routed
+    # through the wrong arm (fx for fy in one `else` arm: 36 % of that term) is small against it.  Per arm and for the rest.  The
+    # adjoint is fed the float64 conics rounded to float32 here (wide_cases.wide_bwd_case: its inputs are then within rounding of
+    # what autograd differentiates, which is what the budget models; the forward's conics are pinned by the test above).
+    cls = b.case.cls
+    groups = dict(xp=cls["xp"], xn=cls["xn"], yp=cls["yp"], yn=cls["yn"], unclamped=~b.case.clamped)
+    for got, ref, bud, name in zip(b.e_c64, b.ref64, b.budget_c64, ("v_means", "v_quats", "v_scales")):
+        err = np.abs(got.astype(np.float64) - ref).max(1)
+        for arm, rows in groups.items():
+            rows = rows & cmp_
+            ratio = err[rows] / bud[rows]
+            print("wide %dx%d %s [%s, %d rows]: max error / budget %.3f" % (Ww, Hw, name, arm, int(rows.sum()), ratio.max()))
+            assert (err[rows] <= bud[rows]).all(), (name, arm, int((ratio > 1).sum()), float(ratio.max()))
+
+
+def test_near_and_far_plane_are_inclusive_and_behind_the_camera_is_culled():
+    """z < near and z > far cull (fully_fused_projection_fwd.cu:96): a Gaussian exactly on either plane is kept, one float
+    below / above is not; z = -1 and z = 0 are culled."""
+    from tests import wide_cases as wc
+    means, quats, scales, vm, K, Wp, Hp, near, far, keep = wc.plane_case()
+    radii, m2, depths, conics = orc.proj_fwd(means, quats, scales, vm, K, Wp, Hp, near=near, far=far)
+    assert np.array_equal(radii > 0, keep), radii
+    assert np.array_equal(depths[keep], means[keep, 2])
+
+
+@pytest.mark.parametrize("Ww,Hw", _wide_sizes())
+def test_radius_clip_culls_radius_equal_to_the_clip(Ww, Hw):
+    """radius <= radius_clip culls (fully_fused_projection_fwd.cu:170): the kept set is {default radius > clip}, rows with a
+    radius exactly on the clip included in the cull."""
+    from tests import wide_cases as wc
+    case = wc.wide_case(Ww, Hw)
+    g = case.g
+    assert (case.r0 == 7).sum() >= 5
+    for clip in wc.RADIUS_CLIPS:
+        radii, m2, depths, conics = orc.proj_fwd(g["means"], g["quats"], g["scales"], case.vm, case.K, Ww, Hw, radius_clip=clip)
+        keep = case.r0 > clip
+        assert keep.sum() > 100 and np.array_equal(radii > 0, keep), clip
+        assert np.array_equal(radii[keep], case.r0[keep]) and np.array_equal(conics[keep], case.c0[keep])

@@ -89,6 +89,94 @@ def test_projection_fwd_bwd(N, W, H):
         assert (err[vis] <= bud[vis]).all(), (name, int((err[vis] > bud[vis]).sum()), float(ratio.max()))
 
 
+def rows_within_budget_or_float64(name, got, orc_out, ref64, bud, rows, classes):
+    """Per-row check of a HIP output against the oracle's on `rows`: the error must stay within the row's condition budget.  A row
+    beyond it is judged against the float64 value: both are float32 roundings of one formula, so the kernel's error against float64
+    may be at most twice the oracle's plus the budget; at most 0.5 % of the rows may need that.  Prints max error / budget per
+    class of `classes` ({label: [N] bool}) -> number of rows that needed the float64 arbitration."""
+    n = got.shape[0]
+    f = lambda a: np.asarray(a, np.float64).reshape(n, -1)
+    got, orc_out, ref64 = f(got), f(orc_out), f(ref64)
+    err = np.abs(got - orc_out).max(1)
+    ratio = err / (bud + 1e-300)
+    for label, m in classes.items():
+        m = m & rows
+        print("%s [%s, %d rows]: max error / budget %.3f (budget / |row| median %.1e)" % (
+            name, label, int(m.sum()), ratio[m].max(), np.median(bud[m] / (np.abs(orc_out[m]).max(1) + 1e-300))))
+    over = rows & (err > bud)
+    if over.any():
+        e_hip, e_orc = np.abs(got - ref64).max(1), np.abs(orc_out - ref64).max(1)
+        worst = (e_hip[over] / (2 * e_orc[over] + bud[over] + 1e-300)).max()
+        print("%s: %d rows beyond their budget, worst (error vs float64) / (2 oracle error + budget) %.3f" % (name, int(over.sum()), worst))
+        assert (e_hip[over] <= 2 * e_orc[over] + bud[over]).all(), (name, int(over.sum()), float(worst))
+        assert over.sum() <= 0.005 * rows.sum(), (name, int(over.sum()))
+    return int(over.sum())
+
+
+@pytest.mark.parametrize("W,H", [(96, 64), (50, 37)])
+def test_projection_fwd_bwd_wide_camera(W, H):
+    """test_projection_fwd_bwd under scenes.wide_camera (fx != fy, off-centre, rotated) on scenes.wide_gaussians: every arm of the
+    field-of-view clamp, rows behind the camera, radii past 100 -- same checks, same allowances."""
+    from gps_slam_amd import gsplat_ops as ops
+    from oracle import splat_ref as orc
+    from tests import wide_cases as wc
+    case, b = wc.wide_case(W, H), wc.wide_bwd_case(W, H)
+    N, g, vm, K = case.N, case.g, case.vm, case.K
+    r0, m0, d0, c0 = case.r0, case.m0, case.d0, case.c0
+    r1, m1, d1, c1 = ops.fully_fused_projection_fwd(T(g["means"]), T(g["quats"]), T(g["scales"]), T(vm)[None], T(K)[None], W, H)
+    r1, m1, d1, c1 = N_(r1)[0], N_(m1)[0], N_(d1)[0], N_(c1)[0]
+    both = (r0 > 0) & (r1 > 0)
+    assert both.sum() > 0.3 * N
+    edge = scenes.radius_is_borderline(c0) | scenes.radius_is_borderline(c1)
+    assert (np.abs(r0 - r1)[both] <= 1).all() and not ((r0 != r1) & both & ~edge).any(), int(((r0 != r1) & both & ~edge).sum())
+    assert ((r0 > 0) != (r1 > 0)).sum() <= 1e-4 * N + 2
+    assert (r1[case.cls["behind"] & ~case.cls["on_near"]] == 0).all()
+    np.testing.assert_allclose(m1[both], m0[both], rtol=1e-4, atol=1e-3)
+    np.testing.assert_allclose(d1[both], d0[both], rtol=1e-5)
+    classes = dict(clamped=case.clamped, unclamped=~case.clamped)
+    cb_ = scenes.condition_budget(lambda mm, qq, ss: (orc.proj_fwd(mm, qq, ss, vm, K, W, H)[3],), (g["means"], g["quats"], g["scales"]), (c0,))[0]
+    _, (_, _, tconic, _, _) = wc.torch_project64(case)
+    rows_within_budget_or_float64("conics", c1, c0, tconic.numpy(), cb_, both, classes)
+    # backward on the oracle's forward state
+    o = ops.fully_fused_projection_bwd(T(g["means"]), T(g["quats"]), T(g["scales"]), T(vm)[None], T(K)[None], W, H, 0.3,
+                                       T(r0)[None], T(c0)[None], T(b.v_m2)[None], T(b.v_d)[None], T(b.v_c)[None])
+    for got, ref, ref64, bud, name in zip(o, b.e, b.ref64, b.budget, ("v_means", "v_quats", "v_scales")):
+        got = N_(got)
+        assert (got[~b.vis] == 0).all(), name
+        rows_within_budget_or_float64(name, got, ref, ref64, bud, b.cmp, classes)
+
+
+def test_projection_cull_planes_keep_a_gaussian_on_the_plane():
+    """near_plane / far_plane other than the defaults: z one float inside, on and one float outside either plane, behind the
+    camera and z = 0 -- the oracle's decisions (pinned in tests/test_oracle_splat.py), bit for bit."""
+    from gps_slam_amd import gsplat_ops as ops
+    from oracle import splat_ref as orc
+    from tests import wide_cases as wc
+    means, quats, scales, vm, K, W, H, near, far, keep = wc.plane_case()
+    e_r, _, e_d, _ = orc.proj_fwd(means, quats, scales, vm, K, W, H, near=near, far=far)
+    r, _, d, _ = ops.fully_fused_projection_fwd(T(means), T(quats), T(scales), T(vm)[None], T(K)[None], W, H, near_plane=near, far_plane=far)
+    assert np.array_equal(e_r > 0, keep) and np.array_equal(N_(r)[0], e_r), (N_(r)[0], e_r)
+    assert np.array_equal(N_(d)[0][keep], e_d[keep])
+
+
+@pytest.mark.parametrize("W,H", [(96, 64), (50, 37)])
+def test_projection_radius_clip_culls_the_radius_on_the_clip(W, H):
+    """radius_clip in {3, 7, 20.5} on the wide scene: wherever the default-parameter radii equal the oracle's, so do the clipped."""
+    from gps_slam_amd import gsplat_ops as ops
+    from oracle import splat_ref as orc
+    from tests import wide_cases as wc
+    case = wc.wide_case(W, H)
+    g = case.g
+    args = (T(g["means"]), T(g["quats"]), T(g["scales"]), T(case.vm)[None], T(case.K)[None], W, H)
+    same = N_(ops.fully_fused_projection_fwd(*args)[0])[0] == case.r0
+    assert same.mean() > 0.99 and ((case.r0 == 7) & same).sum() >= 5
+    for clip in wc.RADIUS_CLIPS:
+        e_r = orc.proj_fwd(g["means"], g["quats"], g["scales"], case.vm, case.K, W, H, radius_clip=clip)[0]
+        r = N_(ops.fully_fused_projection_fwd(*args, radius_clip=clip)[0])[0]
+        assert np.array_equal(r[same], e_r[same]), clip
+        assert np.array_equal(e_r > 0, case.r0 > clip)
+
+
 @pytest.mark.parametrize("deg", [0, 1, 2, 3, 4])
 def test_sh_fwd_bwd(deg):
     from gps_slam_amd import gsplat_ops as ops
@@ -573,17 +661,32 @@ def test_fused_adam_is_bit_identical_to_separate_step():
     small tensors per thread) must leave exactly the parameters / exp_avg / exp_avg_sq that gps_gauss_preprocess_bwd +
     gps_adam_step produce, for several steps, and the same gradients where they are requested.  N is not a multiple of the
     workgroup rows (tail tile)."""
+    N, W, H = 10007, 160, 120
+    g, vm, K, c2w = _setup(N, W, H, seed=11)
+    _fused_adam_against_separate_step(N, W, H, g, vm, K, c2w[:3, 3].copy())
+
+
+@pytest.mark.parametrize("N", [4000, 257])
+def test_fused_adam_is_bit_identical_to_separate_step_under_the_wide_camera(N):
+    """The same under scenes.wide_camera on a prefix of scenes.wide_gaussians (clamped rows, rows behind the camera, radii past
+    100), with the five small tensors stepped in the kernel and not (small5 set and NULL)."""
+    from tests import wide_cases as wc
+    W, H = 96, 64
+    case = wc.wide_case(W, H)
+    g = {k: np.ascontiguousarray(v[:N]) for k, v in case.g.items()}
+    _fused_adam_against_separate_step(N, W, H, g, case.vm, case.K, case.cam_pos)
+
+
+def _fused_adam_against_separate_step(N, W, H, g, vm, K, cam_pos):
     import ctypes as C
     from gps_slam_amd import gsplat_ops as ops
     from gps_slam_amd._lib import AdamSegment, check, lib
-    N, W, H = 10007, 160, 120
-    g, vm, K, c2w = _setup(N, W, H, seed=11)
     sh = T(g["sh"])
     names = ("means", "ls", "q", "ol", "dc", "rest")
     P0 = dict(means=T(g["means"]), ls=T(g["log_scales"]), q=T(g["quats"]), ol=T(g["opac_logit"]).view(-1).contiguous(),
               dc=sh[:, 0].contiguous(), rest=sh[:, 1:].contiguous())
     lrs = dict(means=1.6e-4, ls=5e-3, q=1e-3, ol=5e-2, dc=2.5e-3, rest=5e-4)
-    vmT, KT, cp = T(vm), T(K), T(c2w[:3, 3].copy())
+    vmT, KT, cp = T(vm), T(K), T(cam_pos)
     gen = torch.Generator().manual_seed(5)
     rnd = lambda *s: torch.randn(*s, generator=gen).to(_dev())
     v_m2, v_con, v_col, v_op = rnd(N, 2), rnd(N, 3), rnd(N, 4), rnd(N)

@@ -374,6 +374,157 @@ def test_sh_degree_4_preprocess_and_train_step(fuse):
     assert torch.isfinite(after).all() and (after != before).any()
 
 
+# ----------------------------------------------------------------------------- the wide camera (tests/scenes.py: wide_camera)
+WIDE_PREFIXES = (4000, 257, 256, 255, 1)   # Gaussians taken as a prefix of the scene: the 256-row workgroup, one more, one less, one
+
+
+def _wide_params(case, n):
+    g = case.g
+    return (g["means"][:n].copy(), g["log_scales"][:n].copy(), g["quats"][:n].copy(), g["sh"][:n, 0].copy(), g["sh"][:n, 1:].copy(),
+            g["opac_logit"][:n].copy())
+
+
+def _check_preprocess_state_against_oracle(P, case, W, H, deg, got, max_radii=100):
+    """stage (a) of the chain test: the fused forward's buffers against the oracle chain on the same parameters"""
+    from oracle import splat_ref as orc
+    n = P[0].shape[0]
+    vm, K, cam_pos = case.vm, case.K, case.cam_pos
+    r0, m0, d0, c0, col0, op0, _, _, _ = _oracle_preprocess(P, vm, K, cam_pos, W, H, max_radii=max_radii if max_radii > 0 else 1 << 30, deg=deg)
+    r1, m1, d1, c1, col1, op1 = got
+    both = (r0 > 0) & (r1 > 0)
+    edge = scenes.radius_is_borderline(c0) | scenes.radius_is_borderline(c1)
+    assert ((r0 > 0) != (r1 > 0)).sum() <= 1e-4 * n + 2
+    assert (np.abs(r0 - r1)[both] <= 1).all() and not ((r0 != r1) & both & ~edge).any()
+    np.testing.assert_allclose(m1[both], m0[both], rtol=1e-4, atol=1e-3)
+    np.testing.assert_allclose(d1[both], d0[both], rtol=1e-5)
+    cbud = scenes.condition_budget(lambda pm, pls, pq: (_oracle_preprocess((pm, pls, pq, P[3], P[4], P[5]), vm, K, cam_pos, W, H, deg=deg)[3],),
+                                   (P[0], P[1], P[2]), (c0,), trials=2)[0]
+    cerr = np.abs(c1.astype(np.float64) - c0).max(1)
+    assert (cerr[both] <= cbud[both]).all(), (int((cerr[both] > cbud[both]).sum()), float((cerr[both] / cbud[both]).max()))
+    np.testing.assert_allclose(col1[both], col0[both], rtol=1e-4, atol=2e-5)
+    np.testing.assert_allclose(op1, op0, rtol=2e-6)
+    return r0, both
+
+
+@pytest.mark.parametrize("W,H,deg", [(96, 64, 3), (50, 37, 3), (96, 64, 4)])
+def test_wide_camera_gauss_preprocess_fwd(W, H, deg):
+    """gps_gauss_preprocess_fwd (what the train step runs) under the wide camera: against the oracle chain, and bit for bit against
+    the operator-level projection -- splat_math.hpp promises every inlined copy of project_gaussian the same bits, clamped rows
+    included; max_gs_radii = 100 clamps the radii past 100 this scene has at 96x64, 0 leaves them."""
+    from gps_slam_amd import gsplat_ops as ops
+    from tests import wide_cases as wc
+    case = wc.wide_case(W, H, sh_k=(deg + 1) ** 2)
+    vmT, KT, cpT = T(case.vm), T(case.K), T(case.cam_pos)
+    for n in WIDE_PREFIXES:
+        P = _wide_params(case, n)
+        Pt = [T(a) for a in P]
+        pr, pm, pd, pc = ops.fully_fused_projection_fwd(Pt[0], Pt[2], torch.exp(Pt[1]), vmT[None], KT[None], W, H)
+        for max_radii in (100, 0):
+            out = ops.gauss_preprocess_fwd(Pt[0], Pt[1], Pt[2], Pt[5].view(-1), Pt[3], Pt[4], deg, vmT, KT, cpT, W, H, max_gs_radii=max_radii)
+            radii, m2, depths, conics, colors, opac = out
+            want_r = pr[0].clamp_max(max_radii) if max_radii > 0 else pr[0]
+            assert torch.equal(radii, want_r), (n, max_radii, int((radii != want_r).sum()))
+            assert torch.equal(m2, pm[0]) and torch.equal(depths, pd[0]) and torch.equal(conics, pc[0]), (n, max_radii)
+            r0, both = _check_preprocess_state_against_oracle(P, case, W, H, deg, [N_(t) for t in out], max_radii=max_radii)
+            if n == case.N:
+                assert both.sum() > 0.5 * n
+                if (W, H) == (96, 64):
+                    assert ((N_(radii) == 100) & (N_(pr)[0] > 100)).sum() >= 50 if max_radii else (N_(radii) > 100).sum() >= 50
+
+
+@pytest.mark.parametrize("W,H,deg", [(96, 64, 3), (50, 37, 3), (96, 64, 4)])
+def test_wide_camera_gauss_preprocess_bwd(W, H, deg):
+    """gps_gauss_preprocess_bwd under the wide camera against the oracle adjoint, every row within its own condition budget (built as
+    stage (f) of the chain test builds it); rows the forward culled get zeros.  Rows within 1e-3 of a clamp limit are left out: the
+    adjoint switches arms there."""
+    from gps_slam_amd import gsplat_ops as ops
+    from tests import wide_cases as wc
+    case = wc.wide_case(W, H, sh_k=(deg + 1) ** 2)
+    vm, K, cam_pos = case.vm, case.K, case.cam_pos
+    vmT, KT, cpT = T(vm), T(K), T(cam_pos)
+    rng = np.random.default_rng(2)
+    V = (rng.normal(size=(case.N, 2)).astype(np.float32), (rng.normal(size=(case.N, 3)) * 0.1).astype(np.float32),
+         rng.normal(size=(case.N, 4)).astype(np.float32), rng.normal(size=case.N).astype(np.float32))
+    for n in WIDE_PREFIXES:
+        P = _wide_params(case, n)
+        Pt = [T(a) for a in P]
+        v_m2, v_con, v_col, v_op = (np.ascontiguousarray(v[:n]) for v in V)
+        radii, m2, depths, conics, colors, opac = ops.gauss_preprocess_fwd(Pt[0], Pt[1], Pt[2], Pt[5].view(-1), Pt[3], Pt[4], deg, vmT, KT, cpT, W, H)
+        out = ops.gauss_preprocess_bwd(Pt[0], Pt[1], Pt[2], Pt[5].view(-1), Pt[3], Pt[4], deg, vmT, KT, cpT, W, H, 0.3,
+                                       radii, conics, T(v_m2), T(v_con), T(v_col), T(v_op))
+        r1, c1 = N_(radii), N_(conics)
+        e_g = _oracle_preprocess_bwd(P, vm, K, cam_pos, W, H, r1, c1, v_m2, v_con, v_col, v_op, deg=deg)
+        fn = lambda pm, pls, pq, pdc, prest, pol, cc, a, b, c, d: _oracle_preprocess_bwd(
+            (pm, pls, pq, pdc, prest, pol), vm, K, cam_pos, W, H, r1, cc, a, b, c, d, deg=deg)
+        budget = scenes.condition_budget(fn, P + (c1, v_m2, v_con, v_col, v_op), e_g, trials=2)
+        o64 = 1.0 / (1.0 + np.exp(-P[5][:, 0].astype(np.float64)))
+        budget[5] = budget[5] + 4 * 2.0 ** -23 * np.abs(v_op.astype(np.float64) * o64)
+        vis = r1 > 0
+        cmp_ = vis & ~case.cls["on_limit"][:n]
+        clamped = case.clamped[:n]
+        # ops order: v_means, v_log_scales, v_quats, v_opac_logit, v_sh_dc, v_sh_rest; oracle order: NAMES
+        g_hip = [N_(out[k]) for k in (0, 1, 2, 4, 5, 3)]
+        for name, got_g, ref_g, bud in zip(("means", "scales", "quats", "featuresDc", "featuresRest", "opacities"), g_hip, e_g, budget):
+            assert (got_g.reshape(n, -1)[~vis] == 0).all() or name == "opacities", (n, name)
+            err = np.abs(got_g.reshape(n, -1).astype(np.float64) - ref_g.reshape(n, -1)).max(1)
+            ratio = err / (bud + 1e-300)
+            if n == case.N:
+                print("wide %dx%d deg %d preprocess bwd %s: max error / budget clamped %.3f, unclamped %.3f" % (
+                    W, H, deg, name, ratio[cmp_ & clamped].max(), ratio[cmp_ & ~clamped].max()))
+            assert (err[cmp_] <= bud[cmp_]).all(), (n, name, int((err[cmp_] > bud[cmp_]).sum()), float(ratio[cmp_].max()))
+
+
+def test_wide_camera_train_step_preprocessing_and_binning():
+    """One train step of SLAMGaussianModel under the wide camera (96x64, strips on): what Camera hands the kernels (K, viewmat,
+    cam_pos) shows in the preprocessing buffers (against the oracle chain) and in the tile lists (bit-equal to the oracle's binning
+    of that state); both Adam modes end with the same bits.  The rasterizer's budgets are pinned elsewhere."""
+    from gps_slam_amd.gs_model import Camera, SLAMGaussianModel
+    from oracle import splat_ref as orc
+    from tests import wide_cases as wc
+    W, H, TS = 96, 64, 16
+    tw, th = math.ceil(W / TS), math.ceil(H / TS)
+    case = wc.wide_case(W, H)
+    N, K = case.N, case.K
+    P = _wide_params(case, N)
+    gen = torch.Generator().manual_seed(7)
+    gt, base = torch.rand((H, W, 3), generator=gen).to(DEV), torch.rand((H, W, 3), generator=gen).to(DEV)
+    ref = (torch.rand((H, W, 1), generator=gen) * 3.5 + 0.5).to(DEV)
+    ref[torch.rand((H, W, 1), generator=gen).to(DEV) < 0.1] = 0.0
+    ends = []
+    for mode in (0, 2):
+        m = SLAMGaussianModel(dict(capacity=1 << 16, fuse_sh_rest_adam=mode, strip_backward=True), device=DEV)
+        m.add_params(dict(means=T(P[0]), scales=T(P[1]), quats=T(P[2]), featuresDc=T(P[3]), featuresRest=T(P[4]), opacities=T(P[5])))
+        m.initOptimizers(-1, 3.3)
+        cam = Camera(0, W, H, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), case.c2w, image=gt, device=DEV)
+        m._step_struct(W, H)
+        m.loss_sum().zero_()
+        m.train_step(cam, ref, base, gt, ref_depth_clamped=m.clamp_ref_depth(ref))
+        torch.cuda.synchronize()
+        B = m._B
+        counts = N_(B["counts"])
+        assert counts[2] == 0, "binning capacity overflow"
+        assert math.isfinite(float(m.loss_sum()[0])) and float(m.loss_sum()[0]) > 0
+        # (a) the preprocessing buffers (depths travel as colors[:, 3])
+        r1, m1, c1, col1, op1 = (N_(B[k][:N]) for k in ("radii", "means2d", "conics", "colors", "opacities"))
+        _, both = _check_preprocess_state_against_oracle(P, case, W, H, 3, (r1, m1, col1[:, 3], c1, col1, op1))
+        assert both.sum() > 0.5 * N and (r1 == 100).sum() >= 50
+        # (b) the binning of that state
+        tpg, ids, flat, ggs, gst, offs = orc.isect_tiles(m1, r1, TS, tw, th)
+        ni = int(counts[0])
+        assert ni == flat.shape[0]
+        assert np.array_equal(N_(B["flatten_ids"][:ni]), flat) and np.array_equal(N_(B["tile_offsets"]), offs.reshape(-1))
+        assert np.array_equal(N_(B["tiles_per_gauss"][:N]), tpg)
+        cc = N_(B["cls_counts"])
+        for k, want in enumerate(scenes.bwd_class_lists(m1, r1, TS, tw, th)):
+            assert int(cc[k]) == want.shape[0] and np.array_equal(N_(B["cls_ids"][k, :want.shape[0]]), want), k
+        assert int(counts[3]) == int((r1 > 0).sum())
+        after = [t.clone() for t in m.opt_gs_params.tensors()]
+        assert all(torch.isfinite(t).all() for t in after) and any((a != T(p)).any() for a, p in zip(after, P))
+        ends.append(after)
+    for a, b in zip(ends[0], ends[1]):
+        assert torch.equal(a, b), "the fused Adam mode must leave the parameters of the gradient-writing mode"
+
+
 @pytest.mark.parametrize("fuse", [0, 1, 2])
 def test_first_step_after_init_optimizers_does_not_read_the_moments(fuse):
     """initOptimizers re-creates the Adam state (raw_gs_model.cpp:654-659, every localOptimize); step 1 of every route takes
