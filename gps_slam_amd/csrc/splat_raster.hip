@@ -141,7 +141,7 @@ __device__ __forceinline__ float compose_l1_pixel(const gps::FwdCompose& fc, [[m
 GPS_TUNABLE_REPORT(GPS_FWD_LIST_SPLIT, 4);
 #ifdef GPS_FWD_STAMPS
 GPS_SWITCH_REPORT(GPS_FWD_STAMPS);
-// probe builds only (tools/probe/fwd_stamps.py): 100 MHz timestamps of workgroup phases, 8 slots per tile (0..5 written)
+// probe builds only (tools/probe/fwd_stamps.py): 100 MHz timestamps of workgroup phases, 8 slots per tile (0..6 written; 6, the group lists, between 2 and 3)
 __device__ unsigned long long gps_fwd_stamps_buf[4096 * 8];
 extern "C" GPS_API void* gps_fwd_stamps() { void* p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(gps_fwd_stamps_buf)); return p; }
 #define FWD_STAMP(k) do { if (threadIdx.x == 0) gps_fwd_stamps_buf[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
@@ -161,6 +161,16 @@ extern "C" GPS_API void* gps_fwd_stamps() { void* p = nullptr; (void)hipGetSymbo
 // survivor) and walks them with v_readlane: no test, no ballot, no data-dependent branch in the loop, and no LDS reads for the
 // ~45 % of a tile's entries that do not reach a given half.  Sums are added in list order inside a part and the parts in order:
 // deterministic; a culled entry would have added +0.
+//   groups    per-group survivor lists, one DPP broadcast per trip (below)                                see LABBOOK.md section 23
+// A wave used to evaluate every survivor of its half on all 128 pixels, while a recorded box averages 12.4 x 10.5 px: most lanes
+// of most trips added zeros.  Now each of the wave's four 16-lane DPP rows owns a 32-pixel group of the half.  The staging thread
+// tests the box against the 8 groups of the tile; the half's survivors (the OR of its groups: the same S, the same parts) carry
+// their four group bits in the survivor word.  A wave ballots each bit over its <= 128 survivors into four wave-private lists
+// of record offsets and walks max(list length) trips: every 16 trips a lane loads one entry of its own group's list, and trip
+// t hands lane t's entry to the whole row with v_mov_b32 row_newbcast:t -- one VALU instruction where v_readlane was, no scalar
+// work added.  A group whose list has run out reads a sentinel record (-log2 opacity = +inf: alpha 0, every sum + 0 * 0).  Part
+// boundaries, the order inside a part and the order of the parts are what they were, and no sum can be -0, so the render is bit
+// for bit the one of round 3; gps_set_raster_fwd_group_cull(0) gives every survivor all four bits (the old trips in this code).
 constexpr int FWD_SPLIT = GPS_FWD_LIST_SPLIT;
 constexpr int FWD_THREADS = 128 * FWD_SPLIT;
 #ifndef GPS_FWD_BATCH
@@ -171,7 +181,35 @@ constexpr int FWD_BATCH = GPS_FWD_BATCH;         // list entries staged per batc
 constexpr int FWD_TRIPS = (FWD_BATCH + FWD_THREADS - 1) / FWD_THREADS;
 constexpr int FWD_SEGS = FWD_BATCH / 64;         // 64-entry segments of a batch (one ballot each)
 constexpr int FWD_VECS = (FWD_BATCH / FWD_SPLIT + 63) / 64;   // registers that hold a part's survivor addresses
-static_assert(FWD_BATCH % 64 == 0 && FWD_BATCH * 3 < 65536, "segments are whole waves; record slots are 16-bit");
+static_assert(FWD_BATCH % 64 == 0 && FWD_BATCH * 3 < 2048, "segments are whole waves; a survivor word = 11 bits of record slot + 4 group bits");
+// The four 16-lane DPP rows of a wave each own one FWD_GW x FWD_GH pixel group of the wave's 16 x 8 half: 8 x 4 (two groups across,
+// two down) or 4 x 8 (four across).  Group g sits at column FWD_GW * (g % FWD_GX), row FWD_GH * (g / FWD_GX) of the half; lane j of
+// its row holds pixel pair j % FWD_PW of group row j / FWD_PW.
+#ifndef GPS_FWD_GROUP_W
+#define GPS_FWD_GROUP_W 8
+#endif
+GPS_TUNABLE_REPORT(GPS_FWD_GROUP_W, 8);
+constexpr int FWD_GW = GPS_FWD_GROUP_W, FWD_GH = 32 / FWD_GW;   // a group's pixels, wide x high
+constexpr int FWD_GX = 16 / FWD_GW, FWD_GY = 8 / FWD_GH;        // groups across / down a half
+constexpr int FWD_PW = FWD_GW / 2;                              // pixel pairs (lanes) per group row
+static_assert(FWD_GW == 8 || FWD_GW == 4, "four groups of 32 pixels per half");
+constexpr int FWD_SEQ_STRIDE = FWD_VECS * 64 + 16;             // a group's list of a wave: <= 64 FWD_VECS entries; + 8 dwords: bank skew
+// v_mov_b32_dpp row_newbcast:T -- every lane gets the value that lane T of its own 16-lane row holds
+template <int T>
+__device__ __forceinline__ int fwd_row_bcast(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + T, 0xf, 0xf, true); }   // (every lane is written: no old value)
+// the set bits of a ballot below this lane (v_mbcnt_lo / _hi)
+__device__ __forceinline__ int fwd_mbcnt(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+// wave_sum over the two compose waves of a tile with the additions paired as when lane 8 r + p held pixel pair p of row r of the
+// half: butterfly steps over the lane bits that hold r's bits 2, 1, 0, then p's bits 2, 1, 0.  Keeps the loss and the exposure
+// gradient what they were, bit for bit, whichever group shape maps lanes to pixels.
+__device__ __forceinline__ float fwd_pixel_sum(float v) {
+    constexpr int order8x4[6] = {32, 8, 4, 16, 2, 1}, order4x8[6] = {8, 4, 2, 32, 16, 1};
+#pragma unroll
+    for (int k = 0; k < 6; k++) v += __shfl_xor(v, FWD_GW == 8 ? order8x4[k] : order4x8[k], 64);
+    return v;
+}
 #define GPS_FWD_PK_NAME raster_ges_fwd_pk_kernel
 #define GPS_FWD_PK_EXPOSURE 0
 #include "splat_raster_fwd_pk.inc"
@@ -430,6 +468,10 @@ __global__ __launch_bounds__(256) void raster_ges_bwd_gs_kernel(
 
 }  // namespace
 
+// gps_set_raster_fwd_group_cull: 1 (default) -> a pixel group of the record forward walks only the entries whose box touches it;
+// 0 -> every group walks its half's whole list (the trip structure before the group lists, in the same code: A/B and test lever)
+static int g_raster_fwd_group_cull = 1;
+
 namespace gps {
 
 int raster_ges_fwd_rec_launch(int N, const float* records, const float* ref_depth_map, int width, int height,
@@ -449,15 +491,16 @@ int raster_ges_fwd_rec_launch(int N, const float* records, const float* ref_dept
     // (experiment, gps_set_frame_chain_reserve bit 1: 14 KB of unused dynamic LDS on top of the 26.7 KB the kernel declares -> 3
     // workgroups of 8 waves per compute unit instead of the 4 that fill every wave slot)
     const size_t pad = (gps::frame_chain_reserve_bits() & 2) ? 14 * 1024 : 0;
+    const int group_cull = __atomic_load_n(&g_raster_fwd_group_cull, __ATOMIC_RELAXED);
     if (exposure) {
         GPS_REQUIRE(compose && exposure->row && exposure->slab);
         launch_kernel(TK_RASTER_FWD, 1, raster_ges_fwd_pk_exposure_kernel, dim3(tw * th), dim3(FWD_THREADS), pad, (hipStream_t)stream,
                       (const float4*)records, ref_depth_map, width, height, tw, th, tile_offsets, flatten_ids, counts, delta_depth,
-                      (float4*)render_colors, render_alphas, fc, *exposure, tile_order);
+                      (float4*)render_colors, render_alphas, fc, *exposure, tile_order, group_cull);
     } else {
         launch_kernel(TK_RASTER_FWD, compose ? 1 : 0, raster_ges_fwd_pk_kernel, dim3(tw * th), dim3(FWD_THREADS), pad, (hipStream_t)stream,
                       (const float4*)records, ref_depth_map, width, height, tw, th, tile_offsets, flatten_ids, counts, delta_depth,
-                      (float4*)render_colors, render_alphas, fc, tile_order);
+                      (float4*)render_colors, render_alphas, fc, tile_order, group_cull);
     }
     GPS_LAUNCH_CHECK();
     return GPS_OK;
@@ -493,6 +536,8 @@ int raster_ges_bwd_gs_launch(int N, const float* means2d, const float* conics, c
 }  // namespace gps
 
 extern "C" {
+
+void gps_set_raster_fwd_group_cull(int on) { __atomic_store_n(&g_raster_fwd_group_cull, on ? 1 : 0, __ATOMIC_RELAXED); }
 
 int gps_raster_ges_fwd(int N, const float* means2d, const float* conics, const float* colors, const float* opacities,
                        const float* ref_depth_map, int width, int height, int tile_size, const int32_t* tile_offsets,

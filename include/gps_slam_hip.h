@@ -208,6 +208,11 @@ GPS_API int gps_raster_ges_bwd_strips(int N, const float *records, const int32_t
  * part-filled second round is then the short lists; iteration 257 -> 248 us), on -> row-major (beside a frame chain the ordered
  * launch is 0.7 % slower).  Results do not depend on it. */
 GPS_API void gps_set_frame_chain_reserve(int on);
+/* A/B and test switch, process-wide, read at launch (no reference counterpart).  The record forward (gps_raster_ges_fwd_rec*,
+ * gps_splat_render, gps_splat_train_step) evaluates an entry of a tile's list only on the 32-pixel groups that the entry's packed
+ * pixel bounds touch; on == 0 makes every group of a 16 x 8 half evaluate every survivor of the half, as before the group lists.
+ * Default on.  Results do not depend on it, bit for bit: outside its bounds an entry adds exact zeros. */
+GPS_API void gps_set_raster_fwd_group_cull(int on);
 /* records[N,12] (the 48-byte records gps_gauss_preprocess_fwd writes, incl. the ellipse bounds) from the operator-level arrays
  * means2d[N,2] conics[N,3] colors[N,4] (rgb + depth) opacities[N] radii[N]: lets a caller that holds those run the strip backward */
 GPS_API int gps_raster_pack_records(int N, const float *means2d, const float *conics, const float *colors,

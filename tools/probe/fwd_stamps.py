@@ -1,6 +1,7 @@
 """Where a tile's workgroup spends its time in the forward rasterizer: a probe build (tools/probe/variant.py stamps splat_raster.hip
 -DGPS_FWD_STAMPS) writes 100 MHz timestamps at workgroup phases; printed relative to the first workgroup's start.
-usage: python tools/probe/fwd_stamps.py tools/probe/libgps_stamps.so"""
+usage: python tools/probe/fwd_stamps.py tools/probe/libs/libgps_stamps.so [--no-group-cull]
+(--no-group-cull: gps_set_raster_fwd_group_cull(0), every pixel group walks its half's whole list)"""
 import ctypes as C
 import os
 import sys
@@ -25,6 +26,8 @@ torch.cuda.synchronize()
 B, st = model._B, model._step
 N = st.N
 L = load_library(sys.argv[1])
+if "--no-group-cull" in sys.argv:
+    L.gps_set_raster_fwd_group_cull(0)
 STAMPS = "--no-stamps" not in sys.argv   # (--no-stamps: just launch the kernel three times, e.g. under a counter collection)
 if STAMPS:
     L.gps_fwd_stamps.restype = C.c_void_p
@@ -41,16 +44,16 @@ if not STAMPS:
     scene.close()
     sys.exit(0)
 hip.hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(L.gps_fwd_stamps()), C.c_size_t(host.nbytes), 2)
-t = host.reshape(4096, 8)[:1200, :6].astype(np.int64)
+t = host.reshape(4096, 8)[:1200, [0, 1, 2, 6, 3, 4, 5]].astype(np.int64)   # (slot 6, the group lists, lies between slots 2 and 3)
 t0 = t[:, 0].min()
 us = (t - t0) / 100.0
-names = ["start", "staged (thread 0)", "after staging barrier", "list done (thread 0)", "after sum barrier", "end"]
+names = ["start", "staged (thread 0)", "after staging barrier", "group lists built (thread 0)", "list done (thread 0)", "after sum barrier", "end"]
 for k, nm in enumerate(names):
     q = np.percentile(us[:, k], [0, 25, 50, 75, 100])
-    print("%-24s min %.1f  q25 %.1f  median %.1f  q75 %.1f  max %.1f us" % (nm, *q))
+    print("%-28s min %.1f  q25 %.1f  median %.1f  q75 %.1f  max %.1f us" % (nm, *q))
 d = np.diff(us, axis=1)
-for k in range(5):
-    print("phase %-22s -> %-22s median %.2f  mean %.2f  max %.2f us" % (names[k], names[k + 1], np.median(d[:, k]), d[:, k].mean(), d[:, k].max()))
+for k in range(6):
+    print("phase %-28s -> %-28s median %.2f  mean %.2f  max %.2f us" % (names[k], names[k + 1], np.median(d[:, k]), d[:, k].mean(), d[:, k].max()))
 first = np.argsort(us[:, 0])
 print("workgroups started within the first 2 us: %d; started after 10 us: %d" % ((us[:, 0] < 2).sum(), (us[:, 0] > 10).sum()))
 scene.close()
