@@ -163,6 +163,8 @@ PROTOTYPES = {
     "gps_nn_index_build": (i32, [i32, vp, vp, i64, vp]),
     "gps_nn_query_workspace_bytes": (i64, [i32]),
     "gps_nn_query": (i32, [i32, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "gps_image_metrics_workspace_bytes": (i64, [i32, i32, i32]),
+    "gps_image_metrics": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     "gps_normal_map": (i32, [i32, i32, vp, vp, vp]),
     "gps_zero_floats": (i32, [i32, vp, vp, vp]),
     "gps_rgba8_to_rgbf": (i32, [i32, vp, vp, vp]),

@@ -60,6 +60,21 @@ __device__ __forceinline__ Point point(float mu1, float e11, float mu2, float e2
     return p;
 }
 __device__ __forceinline__ float value(const Point& p) { return (p.C * p.D) / (p.A * p.B); }
+// value(point(...)) AS gps_ssim_fwd's KERNEL COMPUTES IT, written out.  point() leaves its a * b + c to the compiler's
+// floating-point contraction, and hipcc fuses a different part of it in every kernel it is inlined into; in ssim_fwd_kernel
+// (splat_ssim.hip, default flags) the two variances become fma(-mu, mu, e) and the covariance does not.  A kernel that must
+// return the operator's values bit for bit (image_metrics.hip) cannot call point() and hope for the same choice: it calls this,
+// where the choice is explicit and contraction is off.  tests/test_image_eval_gpu.py holds the two together.
+// The sequence is not symmetric in the two images (sigma12 rounds mu1 mu2 first, the variances do not): on IDENTICAL windows it
+// returns 1 +- ~1e-6, not 1.
+__device__ __forceinline__ float value_as_operator(float mu1, float e11, float mu2, float e22, float e12, float C1, float C2) {
+#pragma clang fp contract(off)
+    const float sigma1_sq = fmaf(-mu1, mu1, e11), sigma2_sq = fmaf(-mu2, mu2, e22);
+    const float mu1_mu2 = mu1 * mu2, sigma12 = e12 - mu1_mu2;
+    const float C = fmaf(mu1_mu2, 2.0f, C1), D = fmaf(sigma12, 2.0f, C2);
+    const float A = (mu1 * mu1 + mu2 * mu2) + C1, B = (sigma1_sq + sigma2_sq) + C2;
+    return (C * D) / (A * B);
+}
 __device__ __forceinline__ float d_mu1(const Point& p) {
     return (p.mu2 * 2.0f * p.D) / (p.A * p.B) - (p.mu2 * 2.0f * p.C) / (p.A * p.B) - (p.mu1 * 2.0f * p.C * p.D) / (p.A * p.A * p.B) +
            (p.mu1 * 2.0f * p.C * p.D) / (p.A * p.B * p.B);

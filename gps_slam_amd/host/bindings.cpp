@@ -190,6 +190,25 @@ PYBIND11_MODULE(_host, m) {
           py::arg("sample_nums") = 1000000, py::arg("seed") = 0);
     m.def("ate", &ate, py::arg("est_c2w"), py::arg("gt_c2w"));
 
+    // ---- image evaluation (image_eval.hpp)
+    py::class_<ImageMetrics>(m, "ImageMetrics")
+        .def_readonly("psnr", &ImageMetrics::psnr)
+        .def_readonly("ssim", &ImageMetrics::ssim)
+        .def_readonly("mse", &ImageMetrics::mse)
+        .def_readonly("sse_u8", &ImageMetrics::sse_u8)
+        .def_readonly("psnr_mean", &ImageMetrics::psnr_mean)
+        .def_readonly("ssim_mean", &ImageMetrics::ssim_mean);
+    py::class_<ImageEvalResult>(m, "ImageEvalResult")
+        .def_readonly("cam_ids", &ImageEvalResult::cam_ids)
+        .def_readonly("psnr", &ImageEvalResult::psnr)
+        .def_readonly("ssim", &ImageEvalResult::ssim)
+        .def_readonly("psnr_mean", &ImageEvalResult::psnr_mean)
+        .def_readonly("ssim_mean", &ImageEvalResult::ssim_mean)
+        .def_readonly("metrics", &ImageEvalResult::metrics);
+    m.def("imageMetrics", [](const torch::Tensor& render, const torch::Tensor& gt, const c10::optional<torch::Tensor>& depth) {
+        return imageMetrics(render, gt, depth ? *depth : torch::Tensor());
+    }, py::arg("render"), py::arg("gt"), py::arg("depth") = py::none());
+
     // ---- TSDF engine
     py::class_<TsdfEngine>(m, "ITMBasicEngine")
         .def(py::init([](int w, int h, float fx, float fy, float cx, float cy, float voxel_size, float mu, float vmin,
@@ -388,6 +407,8 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("gt_points_or_triangles"), py::arg("transform") = py::none(), py::arg("dist_thres") = std::vector<double>{0.03},
              py::arg("sample_nums") = 1000000, py::arg("seed") = 0)
         .def("evalTrajectory", &SLAMPipeline::evalTrajectory, py::call_guard<py::gil_scoped_release>())
+        .def("evalImages", &SLAMPipeline::evalImages, py::arg("cams"), py::arg("depth_mask") = false, py::arg("source") = "rgb",
+             py::call_guard<py::gil_scoped_release>())
         .def("saveMesh", &SLAMPipeline::saveMesh)
         .def("saveEngine", &SLAMPipeline::saveEngine)
         .def("loadEngine", &SLAMPipeline::loadEngine)

@@ -593,44 +593,74 @@ void SLAMPipeline::removeRedundantGs() {
 }
 
 // ------------------------------------------------------------------ renderEvalImgs :588-695 (tensors instead of image files)
+TensorDict SLAMPipeline::renderEvalCam(const Camera& cam, const std::vector<std::string>& names) {
+    TensorDict r;
+    TORCH_CHECK(cam.on_device(), "Camera::toGPU() must run before the camera is rendered");
+    auto rc = runRaycastByCam(cam, false);
+    r["raycast_color"] = rc.at("color_map");
+    r["raycast_depth"] = rc.at("depth_map");
+    // what the reference writes to disk, as it quantises it (cv_utils.cpp:57-76 tensorToImage: (t * 255.0).toType(kU8),
+    // truncation; :79-101 tensorToDepth: convertTo(CV_16UC1, 1000) = saturate_cast<ushort>(round-half-even(d * 1000)))
+    r["raycast_color_u8"] = (r["raycast_color"] * 255.0).toType(torch::kUInt8);
+    r["raycast_depth_u16"] = torch::round(r["raycast_depth"] * 1000.0f).clamp(0.0, 65535.0).to(torch::kInt32);
+    if (cam.image.defined()) r["gt_u8"] = (cam.image.to(device) * 255.0).toType(torch::kUInt8);
+    if (model->getGaussianNum() > 0) {
+        auto res = model->forward(cam, rc.at("depth_map"), rc.at("color_map"));
+        for (const std::string& name : names) {
+            if (name == "rgb") {
+                r["rgb"] = torch::clamp(res.at("rgb"), 0, 1);
+                r["rgb_u8"] = (r["rgb"] * 255.0).toType(torch::kUInt8);   // render/<frame>.color.jpg before the JPEG encoder
+                if (cam.image.defined()) {
+                    auto mse = torch::mean(torch::square(r["rgb"] - cam.image.to(device)));
+                    r["psnr"] = -10.0 * torch::log10(mse);
+                    // the number the reference reports: scripts/metric.py reads the 8-bit render / gt files back as
+                    // u8 / 255 (to_tensor) and takes 20 log10(1 / sqrt(mse)) (scripts/utils/image_utils.py:19-21); the lossy
+                    // JPEG encoder in between is I/O outside this library
+                    auto a = r["rgb_u8"].to(torch::kFloat32) / 255.0f, b = r["gt_u8"].to(torch::kFloat32) / 255.0f;
+                    r["psnr_u8"] = 20.0 * torch::log10(1.0 / torch::sqrt(torch::mean(torch::square(a - b))));
+                }
+            } else if (name == "alpha" || name == "depth") {
+                r[name] = res.at(name).clone();
+            }
+        }
+        if (r.count("rgb")) r["rgb"] = r["rgb"].clone();  // forward() returns views of buffers the next camera overwrites
+    }
+    return r;
+}
+
 std::vector<TensorDict> SLAMPipeline::renderEvalImgs(const std::vector<Camera>& cams, const std::vector<std::string>& names) {
     torch::NoGradGuard no_grad;
     flush();
     std::vector<TensorDict> out;
+    for (const Camera& cam : cams) out.push_back(renderEvalCam(cam, names));
+    return out;
+}
+
+// ------------------------------------------------------------------ image evaluation (image_eval.hpp): scripts/metric.py on tensors
+ImageEvalResult SLAMPipeline::evalImages(const std::vector<Camera>& cams, bool depth_mask, const std::string& source) {
+    torch::NoGradGuard no_grad;
+    flush();
+    TORCH_CHECK(source == "rgb" || source == "raycast_color", "evalImages: unknown source '", source, "' (rgb or raycast_color)");
+    TORCH_CHECK(!cams.empty(), "evalImages: no cameras");
+    const std::string key = source + "_u8";
+    std::vector<torch::Tensor> renders, gts, depths;
+    ImageEvalResult out;
     for (const Camera& cam : cams) {
-        TensorDict r;
-        TORCH_CHECK(cam.on_device(), "Camera::toGPU() must run before the camera is rendered");
-        auto rc = runRaycastByCam(cam, false);
-        r["raycast_color"] = rc.at("color_map");
-        r["raycast_depth"] = rc.at("depth_map");
-        // what the reference writes to disk, as it quantises it (cv_utils.cpp:57-76 tensorToImage: (t * 255.0).toType(kU8),
-        // truncation; :79-101 tensorToDepth: convertTo(CV_16UC1, 1000) = saturate_cast<ushort>(round-half-even(d * 1000)))
-        r["raycast_color_u8"] = (r["raycast_color"] * 255.0).toType(torch::kUInt8);
-        r["raycast_depth_u16"] = torch::round(r["raycast_depth"] * 1000.0f).clamp(0.0, 65535.0).to(torch::kInt32);
-        if (cam.image.defined()) r["gt_u8"] = (cam.image.to(device) * 255.0).toType(torch::kUInt8);
-        if (model->getGaussianNum() > 0) {
-            auto res = model->forward(cam, rc.at("depth_map"), rc.at("color_map"));
-            for (const std::string& name : names) {
-                if (name == "rgb") {
-                    r["rgb"] = torch::clamp(res.at("rgb"), 0, 1);
-                    r["rgb_u8"] = (r["rgb"] * 255.0).toType(torch::kUInt8);   // render/<frame>.color.jpg before the JPEG encoder
-                    if (cam.image.defined()) {
-                        auto mse = torch::mean(torch::square(r["rgb"] - cam.image.to(device)));
-                        r["psnr"] = -10.0 * torch::log10(mse);
-                        // the number the reference reports: scripts/metric.py reads the 8-bit render / gt files back as
-                        // u8 / 255 (to_tensor) and takes 20 log10(1 / sqrt(mse)) (scripts/utils/image_utils.py:19-21); the lossy
-                        // JPEG encoder in between is I/O outside this library
-                        auto a = r["rgb_u8"].to(torch::kFloat32) / 255.0f, b = r["gt_u8"].to(torch::kFloat32) / 255.0f;
-                        r["psnr_u8"] = 20.0 * torch::log10(1.0 / torch::sqrt(torch::mean(torch::square(a - b))));
-                    }
-                } else if (name == "alpha" || name == "depth") {
-                    r[name] = res.at(name).clone();
-                }
-            }
-            if (r.count("rgb")) r["rgb"] = r["rgb"].clone();  // forward() returns views of buffers the next camera overwrites
-        }
-        out.push_back(r);
+        TORCH_CHECK(cam.image.defined(), "evalImages: camera ", cam.id, " has no image");
+        if (depth_mask) TORCH_CHECK(cam.has_depth && cam.depth.defined(), "evalImages: depth_mask needs a depth, camera ", cam.id, " has none");
+        TensorDict r = renderEvalCam(cam, {"rgb"});
+        TORCH_CHECK(r.count(key), "evalImages: source '", source, "' needs a model with Gaussians");
+        renders.push_back(r.at(key));
+        gts.push_back(r.at("gt_u8"));
+        if (depth_mask) depths.push_back(cam.depth.to(device, torch::kFloat32).reshape({cam.height, cam.width}));
+        out.cam_ids.push_back(cam.id);
     }
+    out.metrics = imageMetrics(torch::stack(renders), torch::stack(gts), depth_mask ? torch::stack(depths) : torch::Tensor());
+    auto psnr = out.metrics.psnr.cpu(), ssim = out.metrics.ssim.cpu();
+    out.psnr.assign(psnr.data_ptr<double>(), psnr.data_ptr<double>() + psnr.numel());
+    out.ssim.assign(ssim.data_ptr<double>(), ssim.data_ptr<double>() + ssim.numel());
+    out.psnr_mean = out.metrics.psnr_mean;
+    out.ssim_mean = out.metrics.ssim_mean;
     return out;
 }
 

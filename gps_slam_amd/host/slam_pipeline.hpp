@@ -23,6 +23,7 @@
 #include "raw_gs_model.hpp"
 #include "infinitam_tools.hpp"
 #include "tsdf_engine.hpp"
+#include "image_eval.hpp"
 
 // dataset_reader.h:26-100 (uniform branch): draw without replacement, refill when exhausted
 template <class T>
@@ -92,6 +93,15 @@ public:
     // and "psnr_u8" = scripts/metric.py's PSNR of the 8-bit render against the 8-bit ground truth.  The JPEG / PNG encoders
     // themselves are I/O outside this library.
     std::vector<TensorDict> renderEvalImgs(const std::vector<Camera>& cams, const std::vector<std::string>& names = {"rgb"});
+
+    // The reference's image-quality numbers for those views (scripts/metric.py, run/eval.py; with depth_mask its masked variant
+    // scripts/metric_general.py): flush(), every camera rendered exactly as renderEvalImgs renders it, "rgb_u8" and "gt_u8" stacked
+    // and ONE imageMetrics call (image_eval.hpp) -> per-view PSNR and SSIM and their means, the content of results.json /
+    // per_view.json as data (file writing and the JPEG encoder stay outside).  source "raycast_color" compares "raycast_color_u8"
+    // instead: the TSDF-colour baseline (the comparison left commented out in metric.py:15).  depth_mask multiplies both images by
+    // cam.depth > 0 and needs has_depth on every camera.  A camera without an image, an unknown source, or source "rgb" on an
+    // empty model throw.
+    ImageEvalResult evalImages(const std::vector<Camera>& cams, bool depth_mask = false, const std::string& source = "rgb");
 
     // slam_pipeline.h:32-49: mesh / engine state files under workspace_dir (empty names are skipped like the reference)
     std::string workspace_dir = ".", saved_mesh, saved_engine;
@@ -256,6 +266,8 @@ private:
     void processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16);
     // one camera's free view on the current stream, un-batched (runRaycastByCam, renderEvalImgs)
     TensorDict raycastCam(const Camera& cam, const std::vector<ORUtils::SE3Pose>& poses);
+    // one camera of renderEvalImgs / evalImages (the caller holds the NoGradGuard and has flushed)
+    TensorDict renderEvalCam(const Camera& cam, const std::vector<std::string>& names);
     // the same for several cameras of one volume state in ONE batched free-view chain.  ev_out != nullptr: on the raycast stream, and
     // *ev_out is the one event behind all results (use_event: record THIS event instead of one of the update's pooled events)
     std::vector<TensorDict> raycastCams(const std::vector<const Camera*>& cams, const std::vector<ORUtils::SE3Pose>& poses,

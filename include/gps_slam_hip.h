@@ -473,6 +473,32 @@ GPS_API int64_t gps_nn_query_workspace_bytes(int Q);
 GPS_API int gps_nn_query(int R, const void *index_ws, int Q, const float *query_points, float *dist2, int32_t *nn_index,
                          int32_t *stats, void *query_ws, int64_t query_ws_bytes, gps_stream stream);
 
+/* ------------------------------------------------------------------ */
+/* Image-quality evaluation: masked MSE (PSNR) and SSIM of K views     */
+/* ------------------------------------------------------------------ */
+
+/* The per-view numbers of the reference's scripts/metric.py and its masked variant scripts/metric_general.py, K views per call,
+ * no map written to memory.  render, gt: [K,H,W,3] interleaved, uint8 (dtype GPS_IMAGE_U8: converted as float(v) / 255.0f, the
+ * correctly rounded division of to_tensor) or float32 (GPS_IMAGE_F32).  depth (may be NULL): float32 [K,H,W]; both images are
+ * MULTIPLIED by depth > 0 (NaN masks) as metric_general.py:62-64 does -- masked pixels are 0 in both images, still count in
+ * every mean and still feed their neighbours' windows; they are not excluded.
+ *   mse[k]    = sum of squared differences / (3 H W) of the images in [0,1] (float64); for uint8 sse_u8[k] / (255^2 3 H W)
+ *   ssim[k]   = mean over 3 H W of the SSIM map (11-tap sigma-1.5 window, zero padding, C1 = 0.01^2, C2 = 0.03^2): the values
+ *               of gps_ssim_fwd on the same float inputs, summed in float64
+ *   sse_u8[k] = the exact integer sum of squared level differences (uint8 input; 0 for float32)
+ * PSNR is 20 log10(1 / sqrt(mse)) on the host (scripts/utils/image_utils.py:19-21; +inf for identical images).
+ * No floating-point atomics: one partial per 32 x 32 tile in the workspace, added per view in tile order by a second launch, so
+ * results are bitwise reproducible and a view's numbers do not depend on K.  workspace: gps_image_metrics_workspace_bytes(K, H, W)
+ * bytes of device memory, 8-byte aligned, no initialisation needed, free for other use between calls.  The size query is negative
+ * for a non-positive argument.  GPS_ERR_ARG, before any launch, for K, H or W <= 0, an unknown dtype, a NULL image or output and a
+ * missing or short workspace.  Two launches, no allocation, no host sync. */
+#define GPS_IMAGE_U8 0
+#define GPS_IMAGE_F32 1
+GPS_API int64_t gps_image_metrics_workspace_bytes(int K, int H, int W);
+GPS_API int gps_image_metrics(int K, int H, int W, int dtype, const void *render, const void *gt, const float *depth,
+                              void *workspace, int64_t workspace_bytes, double *mse, double *ssim, int64_t *sse_u8,
+                              gps_stream stream);
+
 /* The sample mask of SLAMPipeline::initNewGaussians (slam/slam_pipeline.cpp:450-526) in one launch instead of ~12 tensor ops:
  *   valid = depth in (depth_vis_min, depth_vis_max) and vertex.sum(-1) != 0
  *   mask  = mean(|src_rgb - image|, -1) > color_error_thres  and  valid  [and alpha < alpha_vis_max, if alpha != NULL]
