@@ -2,7 +2,7 @@
 // C++ classes a C++ slam_trainer would link against.
 #include <torch/extension.h>
 
-#include "slam_pipeline.hpp"
+#include "session.hpp"
 
 namespace py = pybind11;
 
@@ -16,8 +16,78 @@ static gpsh::Config config_from_dict(const py::dict& d) {
     return c;
 }
 
+// gpsh::Node -> nested dict / list / str (None for a null), in file order
+static py::object node_to_python(const gpsh::Node& n) {
+    if (n.IsMap()) {
+        py::dict d;
+        for (const auto& kv : n) d[py::str(kv.first)] = node_to_python(kv.second);
+        return std::move(d);
+    }
+    if (n.IsSequence()) {
+        py::list l;
+        for (const gpsh::Node& e : n.elements()) l.append(node_to_python(e));
+        return std::move(l);
+    }
+    if (n.IsScalar()) return py::str(n.text());
+    if (n.IsNull()) return py::none();
+    throw gpsh::ConfigError((n.path().empty() ? std::string("<root>") : n.path()) + ": key is missing");
+}
+
+// the current value of every configuration field, through the entry point's one key list (config_fields.hpp): "settings()"
+namespace {
+struct FieldDumper {
+    py::dict out;
+    std::string prefix;
+    FieldDumper section(const char* k) const { return FieldDumper{out, prefix + k + "."}; }
+    template <class T> void put(const char* k, const T& v) { out[py::str(prefix + k)] = v; }
+    void i(const char* k, int& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
+    void i64(const char* k, int64_t& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
+    void f(const char* k, float& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
+    void d(const char* k, double& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
+    void b(const char* k, bool& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
+    void s(const char* k, std::string& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
+    void ignored(const char*) {}
+};
+}  // namespace
+
 PYBIND11_MODULE(_host, m) {
     m.doc() = "C++ host layer of gps_slam_amd over the C-ABI (libgpsslam_hip.so)";
+
+    // ---- configuration files (config_node.hpp): a gpsh::ConfigError arrives as ConfigError(ValueError) with the same message
+    py::register_exception<gpsh::ConfigError>(m, "ConfigError", PyExc_ValueError);
+    py::class_<gpsh::Node>(m, "Node")
+        .def("__getitem__", [](const gpsh::Node& n, const std::string& k) { return n[k]; })
+        .def("__getitem__", [](const gpsh::Node& n, int64_t i) { return i < 0 ? n[(int)-1] : n[(size_t)i]; })
+        // (indexing never raises, as in C++: an out-of-range index is an undefined node -- so iteration is defined here and does
+        // not fall back to Python's index protocol, which would never end) a map gives its keys, a sequence its elements
+        .def("__iter__", [](const gpsh::Node& n) -> py::object {
+            py::list items;
+            if (n.IsMap()) for (const auto& kv : n) items.append(py::str(kv.first));
+            else if (n.IsSequence()) for (const gpsh::Node& e : n.elements()) items.append(py::cast(e));
+            else throw py::type_error("a scalar, null or undefined Node is not iterable");
+            return items.attr("__iter__")();
+        })
+        .def("__len__", &gpsh::Node::size)
+        .def("size", &gpsh::Node::size)
+        .def("IsDefined", &gpsh::Node::IsDefined)
+        .def("IsNull", &gpsh::Node::IsNull)
+        .def("IsScalar", &gpsh::Node::IsScalar)
+        .def("IsSequence", &gpsh::Node::IsSequence)
+        .def("IsMap", &gpsh::Node::IsMap)
+        .def("keys", [](const gpsh::Node& n) { std::vector<std::string> k; for (const auto& kv : n) k.push_back(kv.first); return k; })
+        .def_property_readonly("path", [](const gpsh::Node& n) { return n.path(); })
+        .def_property_readonly("line", &gpsh::Node::line)
+        .def("to_python", &node_to_python)
+        .def("as_int", [](const gpsh::Node& n) { return n.as<int>(); })
+        .def("as_int64", [](const gpsh::Node& n) { return n.as<int64_t>(); })
+        .def("as_float", [](const gpsh::Node& n) { return n.as<float>(); })
+        .def("as_double", [](const gpsh::Node& n) { return n.as<double>(); })
+        .def("as_bool", [](const gpsh::Node& n) { return n.as<bool>(); })
+        .def("as_str", [](const gpsh::Node& n) { return n.as<std::string>(); })
+        .def("as_float_list", [](const gpsh::Node& n) { return n.as<std::vector<float>>(); })
+        .def("as_int_list", [](const gpsh::Node& n) { return n.as<std::vector<int>>(); });
+    m.def("parse_yaml", &gpsh::parseYaml, py::arg("text"), py::arg("name") = "");
+    m.def("load_yaml", &gpsh::loadYamlFile, py::arg("path"));
 
     // ---- operator surface (gsplat_wapper.hpp)
     m.def("SphericalHarmonicsNew", [](int deg, torch::Tensor dirs, torch::Tensor coeffs, torch::Tensor masks) {
@@ -88,6 +158,7 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("depth", &Camera::depth)
         .def_readwrite("c2w", &Camera::c2w)
         .def_readwrite("c2w_slam", &Camera::c2w_slam)
+        .def_readwrite("img_name", &Camera::img_name)
         .def("toGPU", [](Camera& c) { c.toGPU(); })
         .def("invalidate", &Camera::invalidate)
         .def("viewmat", &Camera::viewmat_tensor)
@@ -115,6 +186,16 @@ PYBIND11_MODULE(_host, m) {
     py::class_<SLAMGaussianModel>(m, "SLAMGaussianModel")
         .def(py::init<>())
         .def("loadConfig", [](SLAMGaussianModel& s, const py::dict& d) { s.loadConfig(config_from_dict(d)); })
+        .def("loadConfig", [](SLAMGaussianModel& s, const gpsh::Node& model_node) { s.loadConfig(model_node); })
+        .def("settings", [](SLAMGaussianModel& s) {
+            FieldDumper dump;
+            int64_t capacity = s.getGaussianParms().capacity();
+            s.configFields(dump, capacity);
+            return dump.out;
+        })
+        .def("saveParamsTensor", &SLAMGaussianModel::saveParamsTensor)
+        .def("saveParamsPly", &SLAMGaussianModel::saveParamsPly)
+        .def("loadParamsTensor", &SLAMGaussianModel::loadParamsTensor)
         .def("forward", &SLAMGaussianModel::forward, py::arg("cam"), py::arg("ref_depth"), py::arg("base_color"))
         .def("rawForward", &SLAMGaussianModel::rawForward)
         .def("setBackgrounds", [](SLAMGaussianModel& s, c10::optional<torch::Tensor> bg) {
@@ -123,6 +204,9 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("render_method", &SLAMGaussianModel::render_method)
         .def("computeLoss", [](SLAMGaussianModel& s, TensorDict& r, const Camera& cam, const py::dict& w) {
             return s.computeLoss(r, cam, config_from_dict(w));
+        })
+        .def("computeLoss", [](SLAMGaussianModel& s, TensorDict& r, const Camera& cam, const gpsh::Node& weight_configs) {
+            return s.computeLoss(r, cam, weight_configs);
         })
         .def("trainStep", [](SLAMGaussianModel& s, const Camera& cam, const torch::Tensor& ref_depth,
                              const torch::Tensor& base_color, c10::optional<torch::Tensor> clamped, const Camera* next_cam,
@@ -289,7 +373,18 @@ PYBIND11_MODULE(_host, m) {
             r->width = w; r->height = h; r->fx = fx; r->fy = fy; r->cx = cx; r->cy = cy;
             return r;
         }))
+        .def(py::init<>())
+        .def("loadConfig", [](DatasetReader& r, const gpsh::Node& reader_node) { r.loadConfig(reader_node); })
+        .def_readwrite("width", &DatasetReader::width)
+        .def_readwrite("height", &DatasetReader::height)
+        .def_readwrite("fx", &DatasetReader::fx)
+        .def_readwrite("fy", &DatasetReader::fy)
+        .def_readwrite("cx", &DatasetReader::cx)
+        .def_readwrite("cy", &DatasetReader::cy)
+        .def_readwrite("scene_scale", &DatasetReader::scene_scale)
+        .def_readwrite("depth_scale", &DatasetReader::depth_scale)
         .def("addTrainCamera", [](DatasetReader& r, const Camera& c) { r.train_vec.push_back(c); })
+        .def("trainCameras", [](DatasetReader& r) { return r.train_vec; })   // copies (c2w_slam: the poses the last session estimated)
         .def("size", [](DatasetReader& r) { return r.train_vec.size(); });
     py::class_<InfiniTAM::Engine::CLIEngine, std::unique_ptr<InfiniTAM::Engine::CLIEngine, py::nodelete>>(m, "CLIEngine")
         .def("ProcessFrame", &InfiniTAM::Engine::CLIEngine::ProcessFrame)
@@ -303,6 +398,8 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("uploadedBytes", &InfiniTAM::Engine::CLIEngine::uploadedBytes)
         .def_readonly("currentFrameNo", &InfiniTAM::Engine::CLIEngine::currentFrameNo);
     m.def("createTsdfEngine", [](const DatasetReader& r, const py::dict& cfg) { return createTsdfEngine(r, config_from_dict(cfg)); },
+          py::return_value_policy::reference);
+    m.def("createTsdfEngine", [](const DatasetReader& r, const gpsh::Node& tsdf_node) { return createTsdfEngine(r, tsdf_node); },
           py::return_value_policy::reference);
 
     // ---- pipeline
@@ -347,6 +444,25 @@ PYBIND11_MODULE(_host, m) {
         .def("processFrameCLI", [](SLAMPipeline& p, int i, Camera& cam) { p.processFrame(i, cam); },
              py::call_guard<py::gil_scoped_release>())
         .def("loadConfig", [](SLAMPipeline& p, const py::dict& d) { p.loadConfig(config_from_dict(d)); })
+        .def("loadConfig", [](SLAMPipeline& p, const gpsh::Node& pipe_node, const std::string& workspace_dir, bool is_train) {
+            p.loadConfig(pipe_node, workspace_dir, is_train);
+        }, py::arg("pipe_node"), py::arg("workspace_dir"), py::arg("is_train"))
+        .def("settings", [](SLAMPipeline& p) {
+            FieldDumper dump;
+            p.configFields(dump);
+            dump.out["workspace_dir"] = p.workspace_dir; dump.out["model_path_full"] = p.model_path;
+            dump.out["log_path_full"] = p.log_path; dump.out["eval_path_full"] = p.eval_path;
+            return dump.out;
+        })
+        .def("save", &SLAMPipeline::save, py::arg("model"), py::arg("cams"), py::call_guard<py::gil_scoped_release>())
+        .def("savePoses", &SLAMPipeline::savePoses, py::arg("dir"), py::arg("cams"))
+        .def("save_poses", &SLAMPipeline::savePoses, py::arg("dir"), py::arg("cams"))
+        .def_readwrite("eval_after_train", &SLAMPipeline::eval_after_train)
+        .def_readwrite("save_after_train", &SLAMPipeline::save_after_train)
+        .def_readonly("model_path", &SLAMPipeline::model_path)
+        .def_readonly("log_path", &SLAMPipeline::log_path)
+        .def_readonly("eval_path", &SLAMPipeline::eval_path)
+        .def_readwrite("scene_scale", &SLAMPipeline::scene_scale)
         // the optimise loop may run the autograd engine (losses beyond L1): it must not hold the GIL
         .def("processFrame", py::overload_cast<int, Camera&, const torch::Tensor&, const torch::Tensor&>(&SLAMPipeline::processFrame),
              py::call_guard<py::gil_scoped_release>())
@@ -413,4 +529,27 @@ PYBIND11_MODULE(_host, m) {
         .def("saveEngine", &SLAMPipeline::saveEngine)
         .def("loadEngine", &SLAMPipeline::loadEngine)
         .def_readwrite("work_mode", &SLAMPipeline::work_mode);
+
+    // ---- the session (session.hpp): slam_trainer.cpp after the reader
+    py::class_<SessionResult>(m, "SessionResult")
+        .def_readonly("work_mode", &SessionResult::work_mode)
+        .def_readonly("workspace_dir", &SessionResult::workspace_dir)
+        .def_readonly("renders", &SessionResult::renders)
+        .def_readonly("image_eval", &SessionResult::image_eval)
+        .def_readonly("has_image_eval", &SessionResult::has_image_eval)
+        .def_readonly("keyframe_count", &SessionResult::keyframe_count)
+        .def_readonly("gaussian_num", &SessionResult::gaussian_num)
+        .def_readonly("times", &SessionResult::times)
+        .def_readonly("files", &SessionResult::files);
+    m.def("run_session", &runSession, py::arg("root"), py::arg("reader"), py::arg("config_filename") = "",
+          py::arg("poses_from_files") = false, py::arg("seed") = 1234, py::call_guard<py::gil_scoped_release>());
+    m.def("create_work_space", &createWorkSpace, py::arg("config_filename"));
+    m.def("cfg_args_line", &cfgArgsLine, py::arg("sh_degree"));
+    m.def("write_cfg_args", &writeCfgArgs, py::arg("file_name"), py::arg("sh_degree"));
+    m.def("cameras_json", &camerasJson, py::arg("cams"));
+    m.def("write_cameras_json", &writeCamerasJson, py::arg("file_name"), py::arg("cams"));
+    m.def("pose_txt", &poseTxt, py::arg("c2w"));
+    m.def("write_pose_txt", &writePoseTxt, py::arg("file_name"), py::arg("c2w"));
+    m.def("read_pose_txt", &readPoseTxt, py::arg("file_name"));
+    m.def("frame_id_of", &frameIdOf, py::arg("cam"), py::arg("fallback_index") = 0);
 }

@@ -218,19 +218,25 @@ CLIEngine* createTsdfEngine(const DatasetReader& data_reader, const Config& conf
     }
     // 3. main engine (:48-63)
     ITMLibSettings* internalSettings = new ITMLibSettings();
-    internalSettings->sceneParams.voxelSize = (float)config.get("voxel_size", 0.005);
-    internalSettings->sceneParams.mu = (float)config.get("trunc_dist", 0.02);
-    internalSettings->sceneParams.viewFrustum_min = (float)config.get("viewFrustum_min", 0.2);
-    internalSettings->sceneParams.viewFrustum_max = (float)config.get("viewFrustum_max", 10.0);
+    TsdfConfig tsdf;   // (its defaults are what a Config without the key has always given)
+    tsdf.sdf_local_block_num = internalSettings->noTotalEntries_blocks;
+    tsdf.sdf_bucket_num = internalSettings->noBuckets;
+    tsdf.sdf_excess_list_size = internalSettings->excessListSize;
+    ConfigReader reader{config};
+    tsdf.configFields(reader);
+    internalSettings->sceneParams.voxelSize = tsdf.voxel_size;
+    internalSettings->sceneParams.mu = tsdf.trunc_dist;
+    internalSettings->sceneParams.viewFrustum_min = tsdf.viewFrustum_min;
+    internalSettings->sceneParams.viewFrustum_max = tsdf.viewFrustum_max;
     // table sizes: compile-time constants of the reference (SDF_LOCAL_BLOCK_NUM 0x40000, SDF_BUCKET_NUM 0x100000, SDF_EXCESS_LIST_SIZE
     // 0x20000, ITMLib/Objects/Scene/ITMVoxelBlockHash.h:15-22) and the defaults here; smaller tables are a test aid (the CPU oracle's
     // per-frame cost is its sweeps over them)
-    internalSettings->noTotalEntries_blocks = (int)config.get("sdf_local_block_num", internalSettings->noTotalEntries_blocks);
-    internalSettings->noBuckets = (int)config.get("sdf_bucket_num", internalSettings->noBuckets);
-    internalSettings->excessListSize = (int)config.get("sdf_excess_list_size", internalSettings->excessListSize);
+    internalSettings->noTotalEntries_blocks = tsdf.sdf_local_block_num;
+    internalSettings->noBuckets = tsdf.sdf_bucket_num;
+    internalSettings->excessListSize = tsdf.sdf_excess_list_size;
     ITMMainEngine* mainEngine =
         new ITMBasicEngine<ITMVoxel, ITMVoxelIndex>(internalSettings, rgbd_calib, rgb_images[0]->noDims, depth_images[0]->noDims);
-    if (config.get("use_gt_pose", 1.0) != 0.0) {
+    if (tsdf.use_gt_pose) {
         auto* be = dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine);
         be->turnOffTracking();
         be->gtC2wPoses = gt_c2w_poses;

@@ -15,6 +15,7 @@
 #include <memory>
 #include <vector>
 
+#include "config_fields.hpp"
 #include "raw_gs_param.hpp"
 #include "tsdf_engine.hpp"
 
@@ -129,10 +130,77 @@ private:
 struct DatasetReader {
     int width = 0, height = 0;
     float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
+    float scene_scale = 1.1f * 3.0f;   // dataset_reader.cpp:231: 1.1 x READER.scene_scale (what slam_trainer.cpp:39 hands the pipeline)
+    float depth_scale = 1000.0f;       // READER.depth_scale: raw depth units per metre (for whoever fills train_vec from files)
     std::vector<Camera> train_vec;
+
+    // The READER node (dataset_reader.cpp:217-231, :342; N = YAML::Node or gpsh::Node): intrinsics, image_shape, scene_scale,
+    // depth_scale.  downscale_factor other than 1 throws (resizing images is reader I/O: DESIGN.md section 8); the paths and the
+    // frame range are for whoever reads the files -- filling train_vec stays the caller's job.
+    template <class N> void loadConfig(const N& reader_node);
+};
+
+// PIPE.TSDF as createTsdfEngine reads it (InfiniTAM_tools.cpp:48-62) + the table sizes this project made runtime parameters
+// (-1: ITMLibSettings' defaults)
+struct TsdfConfig {
+    float voxel_size = 0.005f, trunc_dist = 0.02f, viewFrustum_min = 0.2f, viewFrustum_max = 10.0f;
+    bool use_gt_pose = true;
+    int sdf_local_block_num = -1, sdf_bucket_num = -1, sdf_excess_list_size = -1;
+    template <class V> void configFields(V& v) {   // THE list of createTsdfEngine's keys (config_fields.hpp)
+        v.f("voxel_size", voxel_size);
+        v.f("trunc_dist", trunc_dist);
+        v.f("viewFrustum_min", viewFrustum_min);
+        v.f("viewFrustum_max", viewFrustum_max);
+        v.b("use_gt_pose", use_gt_pose);
+        v.i("sdf_local_block_num", sdf_local_block_num, gpsh::kOptional);
+        v.i("sdf_bucket_num", sdf_bucket_num, gpsh::kOptional);
+        v.i("sdf_excess_list_size", sdf_excess_list_size, gpsh::kOptional);
+        for (const char* k : {"load_images", "saved_mesh", "saved_engine", "saved_images"}) v.ignored(k);   // (the pipeline's: SLAMPipeline::loadConfig)
+    }
 };
 
 // slam/InfiniTAM_tools.cpp:3-67.  config keys: voxel_size, trunc_dist, viewFrustum_min, viewFrustum_max, use_gt_pose (0/1).
 // Image conversion as the reference: rgb = (image * 255).toType(uint8), alpha 255 (cv_utils.cpp:57-76, 221-246);
 // depth = round-half-even(depth * 1000) saturated to uint16, stored in shorts (cv_utils.cpp:79-101, 248-268).
 InfiniTAM::Engine::CLIEngine* createTsdfEngine(const DatasetReader& data_reader, const gpsh::Config& config);
+// the reference's signature: the PIPE.TSDF node (N = YAML::Node or gpsh::Node).  Its five keys are required; a missing one throws
+// before an image is converted.
+template <class N>
+InfiniTAM::Engine::CLIEngine* createTsdfEngine(const DatasetReader& data_reader, const N& tsdf_node) {
+    TsdfConfig t;
+    return createTsdfEngine(data_reader, gpsh::flattenNode(tsdf_node, "PIPE.TSDF", [&](auto& v) { t.configFields(v); }));
+}
+
+// THE list of READER keys (dataset_reader.cpp:217-231, :342) that DatasetReader::loadConfig reads, and those it leaves to whoever
+// reads the files
+struct ReaderConfig {
+    std::vector<float> intrinsics;
+    std::vector<int> image_shape;
+    float downscale_factor = 1.0f, scene_scale = 1.0f, depth_scale = 1000.0f;
+    template <class V> void configFields(V& v) {
+        v.fv("intrinsics", intrinsics);
+        v.iv("image_shape", image_shape);
+        v.f("downscale_factor", downscale_factor);
+        v.f("scene_scale", scene_scale);
+        v.f("depth_scale", depth_scale);
+        for (const char* k : {"input_dir", "image_path", "pose_path", "depth_path", "pcd_name", "start_frame", "end_frame", "frame_step",
+                              "test_split_interval"})
+            v.ignored(k);
+    }
+};
+
+template <class N>
+void DatasetReader::loadConfig(const N& reader_node) {
+    const std::string path = gpsh::nodePath(reader_node, "READER");
+    ReaderConfig r;
+    gpsh::rejectUnknownKeys(reader_node, [&](auto& v) { r.configFields(v); });
+    gpsh::NodeAssigner<N> assign{reader_node, path};
+    r.configFields(assign);
+    if (r.intrinsics.size() < 4) throw gpsh::ConfigError(path + ".intrinsics: four numbers are needed (fx, fy, cx, cy)");
+    if (r.image_shape.size() < 2) throw gpsh::ConfigError(path + ".image_shape: two numbers are needed (width, height)");
+    if (r.downscale_factor != 1.0f) throw gpsh::ConfigError(path + ".downscale_factor: only 1 is supported (images are not resized here)");
+    fx = r.intrinsics[0]; fy = r.intrinsics[1]; cx = r.intrinsics[2]; cy = r.intrinsics[3];
+    width = r.image_shape[0]; height = r.image_shape[1];
+    scene_scale = 1.1f * r.scene_scale;
+    depth_scale = r.depth_scale;
+}

@@ -16,25 +16,36 @@ using torch::indexing::Slice;
 // gps_splat_step::lr order = means, log_scales, quats, sh_dc, sh_rest, opac_logit (the same).
 
 void RawGaussianModel::loadConfig(const Config& c) {
-    maxSH = (int)c.get("sh_degree", maxSH);
+    // every key, with the field it goes to: configFields (raw_gs_model.hpp); a key the Config lacks leaves its field as it is
+    int64_t cap = 1 << 19;
+    ConfigReader reader{c};
+    configFields(reader, cap);
     degreesToUse = maxSH;
-    shDegreeInterval = (int)c.get("sh_degree_interval", shDegreeInterval);
-    max_gs_radii = (int)c.get("max_gs_radii", max_gs_radii);
-    delta_depth = (float)c.get("delta_depth", delta_depth);
-    maxInitScale = (float)c.get("max_init_scale", maxInitScale);
-    minInitScale = (float)c.get("min_init_scale", minInitScale);
-    defaultOpacities = (float)c.get("default_opacities", defaultOpacities);
-    means_lr = c.get("means_lr", means_lr); scales_lr = c.get("scales_lr", scales_lr);
-    quats_lr = c.get("quats_lr", quats_lr); featuresDc_lr = c.get("featuresDc_lr", featuresDc_lr);
-    featuresRest_lr = c.get("featuresRest_lr", featuresRest_lr); opacities_lr = c.get("opacities_lr", opacities_lr);
-    isect_capacity = (int64_t)c.get("isect_capacity", (double)isect_capacity);
-    fuse_sh_rest_adam = c.get("fuse_sh_rest_adam", fuse_sh_rest_adam ? 1.0 : 0.0) != 0.0;
-    strip_backward = c.get("strip_backward", strip_backward ? 1.0 : 0.0) != 0.0;
-    render_method = c.gets("render_method", render_method);
-    use_exposure = c.get("use_exposure", use_exposure ? 1.0 : 0.0) != 0.0;
-    exposure_lr = c.get("exposure_lr", exposure_lr);
-    const int64_t cap = (int64_t)c.get("capacity", 1 << 19);
     opt_gs_params.reserve(cap, numShBases(maxSH), device);
+}
+
+void RawGaussianModel::loadParamsTensor(const std::string& filename) {
+    RawGaussianParams& p = opt_gs_params;
+    if (!p.buffer(0).defined()) p.reserve(1 << 19, numShBases(maxSH), device);
+    {
+        // the archive's SH width must be the configured one (the rows are copied into [capacity, K - 1, 3] storage)
+        torch::serialize::InputArchive archive;
+        archive.load_from(filename);
+        torch::Tensor rest;
+        archive.read("featuresRest", rest);
+        TORCH_CHECK(rest.dim() == 3 && rest.size(1) == p.shK() - 1, "loadParamsTensor: ", filename, " holds ", rest.size(1) + 1,
+                    " SH bases per Gaussian, the model is configured for ", p.shK(), " (sh_degree)");
+    }
+    p.loadTensor(filename);
+    // no optimisers, nothing in flight that refers to the rows that were there before
+    have_opt_ = false;
+    adam_step_ = 0;
+    exp_step_ = 0;
+    exp_state_rows_ = 0;
+    pending_prunes_.clear();
+    prefetched_ = PrefetchKey();
+    leaf_.clear();
+    degreesToUse = maxSH;
 }
 
 void RawGaussianModel::updateSH(int curr_iter) {
@@ -374,7 +385,9 @@ TensorDict RawGaussianModel::computeLoss(TensorDict& render_res, const Camera& c
     auto l1 = mask.defined() ? torch::mean(torch::abs(gt_rgb.masked_select(mask) - rendered_rgb.masked_select(mask)))
                              : torch::mean(torch::abs(gt_rgb - rendered_rgb));  // tensor_math.cpp:41-44
     torch::Tensor rgb_loss;
-    const float ssimWeight = (float)w.get("ssim_weight", 0.0);
+    float ssimWeight = 0.f, depth_weight = 0.f;
+    ConfigReader weights{w};
+    lossWeightFields(weights, ssimWeight, depth_weight);
     if (ssimWeight > 0) {
         const float C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
         auto ssimLoss = 1.0f - FusedSSIMMap::apply((double)C1, (double)C2, rendered_rgb.permute({2, 0, 1}).unsqueeze(0),
@@ -386,7 +399,6 @@ TensorDict RawGaussianModel::computeLoss(TensorDict& render_res, const Camera& c
     TensorDict out;
     out["total"] = rgb_loss;
     out["rgb"] = rgb_loss;
-    const float depth_weight = (float)w.get("depth_weight", 0.0);
     if (depth_weight > 0 && cam.has_depth) {
         auto gt_depth = cam.depth.to(device);
         const auto& rendered_depth = render_res.at("depth");

@@ -8,6 +8,7 @@
 //   * trainStep() is the same iteration as ONE C-ABI call (gps_splat_train_step: 10 launch sites, no host sync, no
 //     autograd graph) -- what SLAMPipeline::localOptimize uses.
 #pragma once
+#include "config_fields.hpp"
 #include "raw_gs_param.hpp"
 
 class RawGaussianModel {
@@ -16,6 +17,12 @@ public:
     ~RawGaussianModel() = default;
 
     void loadConfig(const gpsh::Config& config);  // MODEL section keys of configs/release/*/*.yaml
+    // the reference's signature (raw_gs_model.h:24, N = YAML::Node; gpsh::Node of config_node.hpp reads the same files): the MODEL
+    // node.  Keys the reference reads are required, this project's own are optional, and with gpsh::Node an unknown key throws
+    // (config_fields.hpp).  The node is flattened and goes through loadConfig(const gpsh::Config&): one list of keys, configFields.
+    template <class N> void loadConfig(const N& model_node);
+    template <class V> void configFields(V& v, int64_t& capacity);
+    template <class N> gpsh::Config flattenConfig(const N& model_node);   // every conversion and check of loadConfig(node), nothing assigned
     void updateSH(int curr_iter = -1);            // raw_gs_model.h:30-36
 
     // raw_gs_model.h:38-50.  -> {"rgb"[H,W,3], "depth"[H,W,1], "alpha"[H,W,1], "radiis"[N], "means2d"[N,2]}
@@ -27,6 +34,20 @@ public:
     // -> {"loss", "l1_loss"}
     TensorDict computeLoss(TensorDict& render_res, const Camera& cam, const gpsh::Config& weight_configs,
                            const torch::Tensor& mask = torch::Tensor());
+    // raw_gs_model.h:52 with the PIPE.weight_configs node (ssim_weight, depth_weight: both required, as the reference reads them)
+    template <class N> TensorDict computeLoss(TensorDict& render_res, const Camera& cam, const N& weight_configs,
+                                              const torch::Tensor& mask = torch::Tensor());
+    template <class V> static void lossWeightFields(V& v, float& ssim_weight, float& depth_weight) {
+        v.f("ssim_weight", ssim_weight);
+        v.f("depth_weight", depth_weight);
+    }
+
+    // raw_gs_model.h:68-83: the parameters as a libtorch archive / 3DGS PLY.  loadParamsTensor leaves a model forward() can render
+    // at once: the rows go into the capacity loadConfig reserved (grown if the file holds more), the exposure table is the
+    // file's, there are no optimisers (initOptimizers() starts training afresh).
+    void saveParamsTensor(const std::string& filename) { opt_gs_params.saveTensor(filename); }
+    void saveParamsPly(const std::string& filename) { opt_gs_params.savePly(filename); }
+    void loadParamsTensor(const std::string& filename);
 
     // One optimise iteration as a single C-ABI call; the L1 loss accumulates in lossSum().
     // next_cam (optional): the camera of the NEXT trainStep() -- its preprocessing forward then runs in the tail of this step's
@@ -197,3 +218,50 @@ public:
     int addGaussians(const Camera& cam, const TensorDict& frame_maps, const torch::Tensor& sample_mask,
                      float new_gs_sample_ratio, int frame_num, c10::optional<at::Generator> seed_gen = c10::nullopt);
 };
+
+// THE list of MODEL keys (src/raw_gs_model.cpp:11-40 of the reference + this project's own), for every route (config_fields.hpp)
+template <class V>
+void RawGaussianModel::configFields(V& v, int64_t& capacity) {
+    v.s("render_method", render_method);
+    v.i("sh_degree", maxSH);
+    v.f("max_init_scale", maxInitScale);
+    v.f("min_init_scale", minInitScale);
+    v.i("sh_degree_interval", shDegreeInterval);
+    v.f("default_opacities", defaultOpacities);
+    // (the reference narrows the rates to float before AdamOptions widens them again; they have been doubles here from the start)
+    v.d("means_lr", means_lr);
+    v.d("scales_lr", scales_lr);
+    v.d("quats_lr", quats_lr);
+    v.d("featuresDc_lr", featuresDc_lr);
+    v.d("featuresRest_lr", featuresRest_lr);
+    v.d("exposure_lr", exposure_lr);
+    v.b("use_exposure", use_exposure);
+    v.d("opacities_lr", opacities_lr);
+    v.i("max_gs_radii", max_gs_radii);
+    v.f("delta_depth", delta_depth);
+    // this project's
+    v.i64("isect_capacity", isect_capacity, gpsh::kOptional);
+    v.b("fuse_sh_rest_adam", fuse_sh_rest_adam, gpsh::kOptional);
+    v.b("strip_backward", strip_backward, gpsh::kOptional);
+    v.i64("capacity", capacity, gpsh::kOptional);
+    // in every shipped file, read by nothing the SLAM loop runs (densification: DESIGN.md section 8)
+    for (const char* k : {"means_lr_final", "densify_start_iter", "densify_end_iter", "densify_interval", "densify_grad_thres",
+                          "densify_large_thres", "split_screen_size", "reset_opacity_interval", "prune_opacity_thres"})
+        v.ignored(k);
+}
+
+template <class N>
+gpsh::Config RawGaussianModel::flattenConfig(const N& model_node) {
+    int64_t capacity = 0;
+    return gpsh::flattenNode(model_node, "MODEL", [&](auto& v) { configFields(v, capacity); });
+}
+
+template <class N>
+void RawGaussianModel::loadConfig(const N& model_node) { loadConfig(flattenConfig(model_node)); }
+
+template <class N>
+TensorDict RawGaussianModel::computeLoss(TensorDict& render_res, const Camera& cam, const N& weight_configs, const torch::Tensor& mask) {
+    float ssim = 0.f, depth = 0.f;
+    return computeLoss(render_res, cam, gpsh::flattenNode(weight_configs, "PIPE.weight_configs",
+                                                          [&](auto& v) { lossWeightFields(v, ssim, depth); }), mask);
+}

@@ -18,6 +18,7 @@ struct Camera {
     torch::Tensor c2w_slam;  // camera to world (SLAM estimate)
     torch::Tensor depth;     // [H,W,1] metres
     torch::Tensor K;
+    std::string img_name;    // file name of the image (fs::path(imgFilePath).filename() of the reference): cameras.json, the pose files' names
 
     Camera() {}
     Camera(int width, int height, float fx, float fy, float cx, float cy, bool has_depth, const torch::Tensor& c2w);

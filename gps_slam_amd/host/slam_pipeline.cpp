@@ -182,30 +182,15 @@ void SLAMPipeline::processFrame(int i, Camera& cam) {
     processFrame(i, cam, torch::Tensor(), torch::Tensor());
 }
 
-void SLAMPipeline::loadConfig(const Config& c) {
-    new_gs_sample_ratio = (float)c.get("new_gs_sample_ratio", new_gs_sample_ratio);
-    color_error_thres = (float)c.get("color_error_thres", color_error_thres);
-    localframe_cam_window_length = (int)c.get("localframe_cam_window_length", localframe_cam_window_length);
-    localframe_cam_window_interval = (int)c.get("localframe_cam_window_interval", localframe_cam_window_interval);
-    local_opt_iters = (int)c.get("local_opt_iters", local_opt_iters);
-    local_opt_interval = (int)c.get("local_opt_interval", local_opt_interval);
-    keyframe_theta_thres = (float)c.get("keyframe_theta_thres", keyframe_theta_thres);
-    keyframe_trans_thres = (float)c.get("keyframe_trans_thres", keyframe_trans_thres);
-    keyframe_select_max = (int)c.get("keyframe_select_max", keyframe_select_max);
-    depth_vis_max = (float)c.get("depth_vis_max", depth_vis_max);
-    depth_vis_min = (float)c.get("depth_vis_min", depth_vis_min);
-    alpha_vis_max = (float)c.get("alpha_vis_max", alpha_vis_max);
-    large_scale_thres = (float)c.get("large_scale_thres", large_scale_thres);
-    small_scale_thres = (float)c.get("small_scale_thres", small_scale_thres);
-    low_opac_thres = (float)c.get("low_opac_thres", low_opac_thres);
-    scene_scale = (float)c.get("scene_scale", scene_scale);
-    work_mode = c.gets("work_mode", work_mode);
-    ssim_weight = (float)c.get("ssim_weight", ssim_weight);    // LOSS section of the configs (office0.yaml:37-39)
-    depth_weight = (float)c.get("depth_weight", depth_weight);
-    fused_loss_terms = c.get("fused_loss_terms", fused_loss_terms ? 1.0 : 0.0) != 0.0;
-    sample_method = c.gets("sample_method", sample_method);   // keyframe_sample_configs
-    loss_thres = (float)c.get("loss_thres", loss_thres);
+void SLAMPipeline::loadConfig(const Config& c) { applyConfig(c, false); }
+
+void SLAMPipeline::applyConfig(const Config& c, bool from_node) {
+    // every key, with the field it goes to: configFields (slam_pipeline.hpp); a key the Config lacks leaves its field as it is
+    ConfigReader reader{c, from_node};
+    configFields(reader);
     TORCH_CHECK(sample_method == "random" || sample_method == "ours", "sample_method: 'random' or 'ours', got '", sample_method, "'");
+    if (log_iter == -1) log_iter = max_iterations - 1;   // src/pipeline.cpp:17-18
+    updatePaths();
 }
 
 // ------------------------------------------------------------------ raycast -> tensors (runRaycastByCam :362-415)

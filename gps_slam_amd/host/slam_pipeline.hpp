@@ -71,6 +71,23 @@ public:
     void processFrame(int i, Camera& cam);  // one iteration of that loop: tsdf_engine->ProcessFrame() + the Gaussian block
 
     void loadConfig(const gpsh::Config& config);  // PIPELINE section keys
+    // The reference's signature (slam_pipeline.cpp:175-193 + Pipeline::loadConfig, src/pipeline.cpp:5-36; N = YAML::Node or
+    // gpsh::Node): the PIPE node with its nested weight_configs / vis_configs / keyframe_sample_configs / remove_configs / TSDF.
+    // The output paths are workspace_dir + the file's strings, as the reference concatenates them; is_train creates the
+    // directories the reference creates (each one emptied first, like its createDirectory(path, true); no TensorBoard logger).
+    // enable_densify: true throws -- densification is out of scope.  One list of keys: configFields.
+    template <class N> void loadConfig(const N& pipe_node, const std::string& workspace_dir, bool is_train);
+    template <class V> void configFields(V& v);
+    // the two halves of the node route: node -> flat Config (every conversion and check, nothing assigned), and the assignment
+    template <class N> gpsh::Config flattenConfig(const N& pipe_node);
+    void applyConfig(const gpsh::Config& flat, bool from_node);
+    void createOutputDirs();   // what loadConfig(node, dir, true) creates
+
+    // Pipeline::save (src/pipeline.cpp:38-54): nothing for an empty model; else model_path/cfg_args, point_cloud/point_cloud.ply,
+    // model.pt and cameras.json (session.hpp: writeCfgArgs, writeCamerasJson) -- a directory 3DGS viewers load.  Returns the files.
+    std::vector<std::string> save(SLAMGaussianModel& model, const std::vector<Camera>& cams);
+    // DatasetReader::savePose (dataset_reader.cpp:405-418): one frame<id>.txt per camera with its c2w_slam (writePoseTxt)
+    std::vector<std::string> savePoses(const std::string& dir, const std::vector<Camera>& cams);
 
     // body of the SLAMTrainCams frame loop (:69-132) for frame i
     void processFrame(int i, Camera& cam, const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16);
@@ -115,6 +132,18 @@ public:
     GeomEvalResult evalGeometry(const torch::Tensor& gt_points_or_triangles, const torch::Tensor& transform = torch::Tensor(),
                                 const std::vector<double>& dist_thres = {0.03}, int64_t sample_nums = 1000000, uint64_t seed = 0);
     AteResult evalTrajectory();
+
+    // Pipeline::loadConfig's session settings (src/pipeline.cpp:9-22).  The *_cfg strings are the file's ("/gs_model", "/log", "/val");
+    // model_path / log_path / eval_path = workspace_dir + them.  max_iterations, selected_cam_idx, log_iter, log_slam_state and
+    // enable_densify are stored only: the SLAM loop uses none of them.
+    bool eval_after_train = false, save_after_train = false, enable_densify = false, log_slam_state = false;
+    int max_iterations = 10000, selected_cam_idx = -1, log_iter = 1000;
+    std::string model_path_cfg = "/gs_model", log_path_cfg = "/log", eval_path_cfg = "/val";
+    std::string model_path, log_path, eval_path, saved_images;
+    float color_error_max = 0.1f, depth_error_max = 0.1f;   // vis_configs of the reference's image logging (stored only)
+    void updatePaths() {
+        model_path = workspace_dir + model_path_cfg; log_path = workspace_dir + log_path_cfg; eval_path = workspace_dir + eval_path_cfg;
+    }
 
     torch::Device device = torch::kCUDA;
     std::string work_mode = "train";
@@ -343,3 +372,94 @@ private:
     void waitAllRaycasts() { waitRaycast(views_.last_event); }   // ... for all of the current update's
     bool map_in_flight_ = false, prune_pending_ = false;
 };
+
+// THE list of PIPE keys (slam_pipeline.cpp:175-193, src/pipeline.cpp:5-36 and the nested sections the reference reads where it uses
+// them: :130, :308, :420-459, :538, :568-570, slam_pipeline.h:32-49), for every route (config_fields.hpp)
+template <class V>
+void SLAMPipeline::configFields(V& v) {
+    v.i("max_iterations", max_iterations);
+    v.i("selected_cam_idx", selected_cam_idx);
+    v.b("enable_densify", enable_densify);
+    v.b("eval_after_train", eval_after_train);
+    v.b("save_after_train", save_after_train);
+    v.i("log_iter", log_iter);
+    v.s("model_path", model_path_cfg);
+    v.s("log_path", log_path_cfg);
+    v.s("eval_path", eval_path_cfg);
+    v.f("new_gs_sample_ratio", new_gs_sample_ratio);
+    v.i("keyframe_select_max", keyframe_select_max);
+    v.i("localframe_cam_window_length", localframe_cam_window_length);
+    v.i("localframe_cam_window_interval", localframe_cam_window_interval);
+    v.i("local_opt_iters", local_opt_iters);
+    v.i("local_opt_interval", local_opt_interval);
+    v.f("color_error_thres", color_error_thres);
+    v.f("keyframe_theta_thres", keyframe_theta_thres);
+    v.f("keyframe_trans_thres", keyframe_trans_thres);
+    v.b("log_slam_state", log_slam_state);
+    {
+        auto w = v.section("weight_configs");   // LOSS weights (office0.yaml:37-39)
+        RawGaussianModel::lossWeightFields(w, ssim_weight, depth_weight);
+    }
+    {
+        auto s = v.section("vis_configs");
+        s.f("color_error_max", color_error_max);
+        s.f("depth_error_max", depth_error_max);
+        s.f("depth_vis_max", depth_vis_max);
+        s.f("depth_vis_min", depth_vis_min);
+        s.f("alpha_vis_max", alpha_vis_max);
+    }
+    {
+        auto s = v.section("keyframe_sample_configs");
+        s.s("sample_method", sample_method);
+        s.f("loss_thres", loss_thres);
+        s.ignored("weight_intervel");   // (in every shipped file, read by nothing)
+        s.ignored("opt_thres");
+    }
+    {
+        auto s = v.section("remove_configs");
+        s.f("large_scale_thres", large_scale_thres);
+        s.f("small_scale_thres", small_scale_thres);
+        s.f("low_opac_thres", low_opac_thres);
+    }
+    {
+        auto s = v.section("TSDF");
+        s.s("saved_mesh", saved_mesh);
+        s.s("saved_engine", saved_engine);
+        s.s("saved_images", saved_images);
+        for (const char* k : {"voxel_size", "trunc_dist", "viewFrustum_min", "viewFrustum_max", "load_images", "use_gt_pose",
+                              "sdf_local_block_num", "sdf_bucket_num", "sdf_excess_list_size"})
+            s.ignored(k);   // (createTsdfEngine's: TsdfConfig)
+    }
+    v.ignored("train_mode");     // (one of the two is in every shipped file; the render method is MODEL.render_method)
+    v.ignored("train_method");
+    // this project's.  The schedule switches are read from a node alone: the flat route never read them and still does not.
+    // (The flat route does accept the session keys above -- model_path, eval_after_train, saved_mesh ... -- which it had no field
+    // for before.)
+    v.b("fused_loss_terms", fused_loss_terms, gpsh::kOptional);
+    v.b("overlap_mapping", overlap_mapping, gpsh::kNodeOnly);
+    v.b("mapping_thread", mapping_thread, gpsh::kNodeOnly);
+    v.b("async_raycasts", async_raycasts, gpsh::kNodeOnly);
+    v.b("pipeline_raycasts", pipeline_raycasts, gpsh::kNodeOnly);
+    v.b("merge_keyframe_raycasts", merge_keyframe_raycasts, gpsh::kNodeOnly);
+    v.b("prefetch_next_preprocess", prefetch_next_preprocess, gpsh::kNodeOnly);
+    v.b("log_pipeline_time", log_pipeline_time, gpsh::kNodeOnly);
+    // the flat route alone: what the nested files keep outside PIPE (READER.scene_scale x 1.1, the root's work_mode)
+    v.f("scene_scale", scene_scale, gpsh::kFlatOnly);
+    v.s("work_mode", work_mode, gpsh::kFlatOnly);
+}
+
+template <class N>
+gpsh::Config SLAMPipeline::flattenConfig(const N& pipe_node) {
+    gpsh::Config flat = gpsh::flattenNode(pipe_node, "PIPE", [&](auto& v) { configFields(v); });
+    if (flat.get("enable_densify", 0.0) != 0.0)
+        throw gpsh::ConfigError(gpsh::nodePath(pipe_node, "PIPE") + ".enable_densify: densification is not supported (set it to false)");
+    return flat;
+}
+
+template <class N>
+void SLAMPipeline::loadConfig(const N& pipe_node, const std::string& workspace_dir_, bool is_train) {
+    const gpsh::Config flat = flattenConfig(pipe_node);
+    workspace_dir = workspace_dir_;
+    applyConfig(flat, true);
+    if (is_train) createOutputDirs();
+}

@@ -80,6 +80,24 @@ class SLAMPipeline:
         self.workspace_dir, self.saved_mesh, self.saved_engine = ".", "", ""
         self.gtC2wPoses = []  # dataset pose of every processed frame (ITMBasicEngine::gtC2wPoses), for evalTrajectory
 
+    @classmethod
+    def from_config(cls, nested, tsdf_engine, model, seed=1234):
+        """The pipeline as slam_trainer.cpp:26-41 sets it up from a config file: `nested` is what config.load_yaml returns.
+        PIPE (with its nested sections folded, config.flatten) -> pipe_cfg; the root's work_mode and workspace_dir;
+        scene_scale = 1.1 x READER.scene_scale (dataset_reader.cpp:231); TSDF.use_gt_pose, saved_mesh, saved_engine."""
+        from . import config
+        flat = config.flatten(nested["PIPE"], config.PIPE_KEYS)
+        if flat["enable_densify"]:
+            raise config.ConfigError("PIPE.enable_densify: densification is not supported (set it to false)")
+        if flat["sample_method"] not in ("random", "ours"):
+            raise config.ConfigError("PIPE.keyframe_sample_configs.sample_method: 'random' or 'ours', got '%s'" % flat["sample_method"])
+        pipe_cfg = {k: flat[k] for k in DEFAULT_PIPE if k in flat}
+        pipe_cfg["scene_scale"] = float(np.float32(1.1) * np.float32(nested["READER"]["scene_scale"].as_float()))
+        pipe = cls(tsdf_engine, model, pipe_cfg, seed=seed, work_mode=nested["work_mode"].as_str(), use_gt_pose=flat["use_gt_pose"])
+        pipe.workspace_dir = nested["workspace_dir"].as_str()
+        pipe.saved_mesh, pipe.saved_engine = flat["saved_mesh"], flat["saved_engine"]
+        return pipe
+
     # ------------------------------------------------------------------ slam_pipeline.h:32-49
     def saveMesh(self):
         if self.saved_mesh:
