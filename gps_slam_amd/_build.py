@@ -19,6 +19,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
 PER_FILE = {
     # file prefix -> extra flags
     "tsdf_": ["-ffp-contract=off"],
+    "reloc_": ["-ffp-contract=off"],   # the blurred image feeds threshold comparisons: the reference's unfused sequence
 }
 
 

@@ -38,7 +38,7 @@ class TrackConfig(C.Structure):
 class TrackState(C.Structure):
     """gps_track_state (host memory)"""
     _fields_ = [("pose_M", f32 * 16), ("pose_invM", f32 * 16), ("pose_pc_M", f32 * 16), ("age_point_cloud", i32),
-                ("frames_processed", i32), ("diag", f32 * 16), ("host_mailbox", vp), ("mail_seq", i32), ("scratch_epoch", i32), ("dev_arg_line", vp), ("mailbox_bytes", i32)]
+                ("frames_processed", i32), ("diag", f32 * 16), ("host_mailbox", vp), ("mail_seq", i32), ("scratch_epoch", i32), ("dev_arg_line", vp), ("mailbox_bytes", i32), ("n_valid_max", i32)]
 
 
 class SplatStep(C.Structure):
@@ -66,6 +66,11 @@ class SplatStep(C.Structure):
 
 class AdamSegment(C.Structure):
     _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", i64), ("lr", f64)]
+
+
+class RelocResult(C.Structure):
+    """gps_reloc_result"""
+    _fields_ = [("added_id", i32), ("n_found", i32), ("ids", i32 * 4), ("distances", f32 * 4), ("n_entries", i32), ("overflow", i32)]
 
 
 # name -> (restype, argtypes); mirrors include/gps_slam_hip.h one to one
@@ -137,6 +142,9 @@ PROTOTYPES = {
                                              vp]),
     "gps_tsdf_process_frame_tracked_gated": (i32, [C.POINTER(TsdfState), vp, C.POINTER(TrackConfig), C.POINTER(TrackState), vp, i64,
                                                    vp, vp, vp]),
+    "gps_tsdf_update_visible_list": (i32, [C.POINTER(TsdfState), vp, vp, i32, vp]),
+    "gps_tsdf_frame_track": (i32, [C.POINTER(TsdfState), vp, C.POINTER(TrackConfig), C.POINTER(TrackState), vp, i64, vp]),
+    "gps_tsdf_frame_map": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), i32, i32, vp]),
     "gps_tsdf_convert_depth": (i32, [C.POINTER(TsdfState), vp, vp]),
     "gps_tsdf_allocate": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_integrate": (i32, [C.POINTER(TsdfState), vp, vp]),
@@ -163,6 +171,20 @@ PROTOTYPES = {
     "gps_nn_index_build": (i32, [i32, vp, vp, i64, vp]),
     "gps_nn_query_workspace_bytes": (i64, [i32]),
     "gps_nn_query": (i32, [i32, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "gps_reloc_gaussian_taps": (i32, [f32, i32, vp, vp]),
+    "gps_reloc_default_ferns": (i32, [i32, i32, i32, i32, f32, f32, C.c_uint64, vp, vp]),
+    "gps_reloc_create": (i32, [C.POINTER(vp), i32, i32, i32, i32, f32, f32, f32, i32, C.c_uint64]),
+    "gps_reloc_destroy": (i32, [vp]),
+    "gps_reloc_info": (i32, [vp, vp]),
+    "gps_reloc_set_ferns": (i32, [vp, vp, vp, i32, vp]),
+    "gps_reloc_get_ferns": (i32, [vp, vp, vp, i32]),
+    "gps_reloc_set_debug_outputs": (i32, [vp, vp, vp]),
+    "gps_reloc_process_frame": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "gps_reloc_read_result": (i32, [vp, C.POINTER(RelocResult), vp]),
+    "gps_reloc_retrieve_pose": (i32, [vp, i32, vp, vp, vp, vp]),
+    "gps_reloc_export": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+    "gps_reloc_import": (i32, [vp, i32, vp, vp, vp, vp]),
+    "gps_reloc_check_guards": (i32, [vp, vp]),
     "gps_image_metrics_workspace_bytes": (i64, [i32, i32, i32]),
     "gps_image_metrics": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     "gps_normal_map": (i32, [i32, i32, vp, vp, vp]),

@@ -114,14 +114,17 @@ __device__ __forceinline__ bool band_begin(const TsdfState& s, const Mat4& invM,
     return true;
 }
 
-__global__ __launch_bounds__(256) void mark_previous_visible_kernel(TsdfState s) {
+// type: 3 = "visible last frame", re-tested against the frustum by the sweep; 0 = the list is dropped (resetVisibleList)
+__global__ __launch_bounds__(256) void mark_previous_visible_kernel(TsdfState s, uint8_t type) {
     GPS_FRAME_PRIO();
     const int n = s.counters[GPS_TSDF_N_VISIBLE];
     const int stride = gridDim.x * blockDim.x;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s.visible_type[s.visible_ids[i]] = 3;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s.visible_type[s.visible_ids[i]] = type;
 }
 
-__global__ __launch_bounds__(256) void alloc_request_kernel(TsdfState s, Mat4 invM) {
+// allocate == 0 (onlyUpdateVisibleList of AllocateSceneFromDepth): blocks the band crosses that exist are marked visible, blocks
+// that do not are left alone -- no request is raised, so nothing is allocated
+__global__ __launch_bounds__(256) void alloc_request_kernel(TsdfState s, Mat4 invM, int allocate) {
     GPS_FRAME_PRIO();
     const int loc = blockIdx.x * blockDim.x + threadIdx.x;
     if (loc >= s.width * s.height) return;
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(256) void alloc_request_kernel(TsdfState s, Mat4 in
                 }
             }
             // last requester in (pixel, step) order wins the slot, like the sequential CPU loop
-            if (!found) atomicMax(&s.alloc_prio[hashIdx], ((uint32_t)(loc + 1) << BAND_STEP_BITS) | (uint32_t)i);
+            if (!found && allocate) atomicMax(&s.alloc_prio[hashIdx], ((uint32_t)(loc + 1) << BAND_STEP_BITS) | (uint32_t)i);
         }
         w.px += w.dx; w.py += w.dy; w.pz += w.dz;
     }
@@ -605,7 +608,9 @@ int gps_tsdf_convert_depth(const gps_tsdf_state* sp, const int16_t* depth_mm, gp
     return GPS_OK;
 }
 
-int gps_tsdf_allocate(const gps_tsdf_state* sp, const float* M, const float* invM, gps_stream stream) {
+// the allocation sweep; allocate == 0: the same sweep with allocation suppressed (ITMDenseMapper::UpdateVisibleList), where
+// reset_visible additionally drops last frame's list instead of re-testing it
+static int allocate_impl(const gps_tsdf_state* sp, const float* M, const float* invM, int allocate, int reset_visible, gps_stream stream) {
     GPS_ENTER();
     GPS_REQUIRE(sp != nullptr && M != nullptr && invM != nullptr);
     GPS_REQUIRE(state_valid(*sp));
@@ -625,11 +630,13 @@ int gps_tsdf_allocate(const gps_tsdf_state* sp, const float* M, const float* inv
     int32_t* blk2 = s.scan_scratch + nblk;
     int32_t* blkv = s.scan_scratch + 2 * nblk;
     int32_t* tot = s.scan_scratch + 3 * nblk;  // [2] totals scratch
-    mark_previous_visible_kernel<<<256, 256, 0, st>>>(s);
-    alloc_request_kernel<<<gps_div_up(P, 256), 256, 0, st>>>(s, im);
-    alloc_count_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, blk1, blk2);
-    scan_counts_kernel<<<1, SCAN_THREADS, 0, st>>>(nblk, blk1, blk2, tot, nullptr);
-    alloc_apply_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, im, blk1, blk2, bucket_bits(s));
+    mark_previous_visible_kernel<<<256, 256, 0, st>>>(s, (uint8_t)(reset_visible ? 0 : 3));
+    alloc_request_kernel<<<gps_div_up(P, 256), 256, 0, st>>>(s, im, allocate);
+    if (allocate) {   // (without requests the three launches below would find nothing to do)
+        alloc_count_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, blk1, blk2);
+        scan_counts_kernel<<<1, SCAN_THREADS, 0, st>>>(nblk, blk1, blk2, tot, nullptr);
+        alloc_apply_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, im, blk1, blk2, bucket_bits(s));
+    }
     // ordered visible list (byte flags live behind the per-block counts in scan_scratch)
     uint8_t* flags = reinterpret_cast<uint8_t*>(s.scan_scratch + 3 * nblk + 16);
     visible_count_kernel<VIS_LIVE><<<nblk, SWEEP_THREADS, 0, st>>>(s, m, blkv, flags, nullptr);
@@ -637,6 +644,14 @@ int gps_tsdf_allocate(const gps_tsdf_state* sp, const float* M, const float* inv
     visible_write_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, blkv, flags, s.visible_ids, s.n_blocks, nullptr);
     GPS_LAUNCH_CHECK();
     return GPS_OK;
+}
+
+int gps_tsdf_allocate(const gps_tsdf_state* sp, const float* M, const float* invM, gps_stream stream) {
+    return allocate_impl(sp, M, invM, 1, 0, stream);
+}
+
+int gps_tsdf_update_visible_list(const gps_tsdf_state* sp, const float* M, const float* invM, int reset_visible, gps_stream stream) {
+    return allocate_impl(sp, M, invM, 0, reset_visible, stream);
 }
 
 int gps_tsdf_find_visible(const gps_tsdf_state* sp, const float* M, gps_stream stream) {

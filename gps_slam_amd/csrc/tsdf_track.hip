@@ -1504,6 +1504,7 @@ static int track_camera_impl(const gps_tsdf_state* sp, const gps_track_config* c
     }
     const int nvalid = lm.nvalid_depth_good; const float f = lm.f_depth_good;
     ts->diag[8] = (float)nvalid; ts->diag[9] = f;
+    ts->n_valid_max = n_max;
     ts->diag[10] = n_max > 0 ? sqrtf(((float)nvalid * f + (float)(n_max - nvalid) * c->space_thresh[0]) / (float)n_max) : 0.0f;
     float det = 0.0f;
     if (lm.last_type == TRK_BOTH) { det = Chol(lm.hessian_depth_good, 6).determinant(); if (isnan(det)) det = 0.0f; }
@@ -1522,9 +1523,12 @@ int gps_tsdf_process_frame_tracked(const gps_tsdf_state* s, const int16_t* depth
     return gps_tsdf_process_frame_tracked_gated(s, depth_mm, cfg, ts, scratch, scratch_bytes, stream, nullptr, nullptr);
 }
 
-int gps_tsdf_process_frame_tracked_gated(const gps_tsdf_state* s, const int16_t* depth_mm, const gps_track_config* cfg,
-                                         gps_track_state* ts, void* scratch, int64_t scratch_bytes, gps_stream stream,
-                                         void (*before_fusion)(void*), void* user) {
+// The two halves of a tracked frame.  gps_tsdf_frame_track: ITMTrackingController::Track (or, without a valid point cloud, only the
+// depth conversion); it only READS the volume.  gps_tsdf_frame_map: ITMDenseMapper::ProcessFrame (fuse != 0) or
+// ITMDenseMapper::UpdateVisibleList (fuse == 0: the same sweep, nothing allocated, nothing integrated; reset_visible drops last
+// frame's visible list), then ITMTrackingController::Prepare at ts->pose.
+int gps_tsdf_frame_track(const gps_tsdf_state* s, const int16_t* depth_mm, const gps_track_config* cfg, gps_track_state* ts,
+                         void* scratch, int64_t scratch_bytes, gps_stream stream) {
     GPS_REQUIRE(s && depth_mm && cfg && ts);
     int r;
     if (ts->age_point_cloud != -1) {  // ITMTrackingState::HasValidPointCloud
@@ -1536,16 +1540,34 @@ int gps_tsdf_process_frame_tracked_gated(const gps_tsdf_state* s, const int16_t*
     } else {
         if ((r = gps_tsdf_convert_depth(s, depth_mm, stream)) != GPS_OK) return r;
     }
-    if (before_fusion) before_fusion(user);  // everything above only READ the volume; what follows modifies it
+    return GPS_OK;
+}
+
+int gps_tsdf_frame_map(const gps_tsdf_state* s, gps_track_state* ts, int fuse, int reset_visible, gps_stream stream) {
+    GPS_REQUIRE(s && ts);
+    int r;
     const double t1 = wall_ms();
-    if ((r = gps_tsdf_allocate(s, ts->pose_M, ts->pose_invM, stream)) != GPS_OK) return r;
-    if ((r = gps_tsdf_integrate(s, ts->pose_M, stream)) != GPS_OK) return r;
+    if (fuse) {
+        if ((r = gps_tsdf_allocate(s, ts->pose_M, ts->pose_invM, stream)) != GPS_OK) return r;
+        if ((r = gps_tsdf_integrate(s, ts->pose_M, stream)) != GPS_OK) return r;
+    } else {
+        if ((r = gps_tsdf_update_visible_list(s, ts->pose_M, ts->pose_invM, reset_visible, stream)) != GPS_OK) return r;
+    }
     if ((r = gps_tsdf_expected_depths_and_raycast(s, ts->pose_M, ts->pose_invM, 0, 1, stream)) != GPS_OK) return r;
     if ((r = gps_tsdf_icp_maps(s, ts->pose_invM, stream)) != GPS_OK) return r;
     memcpy(ts->pose_pc_M, ts->pose_M, 64);  // pose_pointCloud := pose_d (ITMTrackingController.h:87-93)
     ts->age_point_cloud = (ts->age_point_cloud == -1) ? -2 : 0;
     ts->diag[15] = (float)(wall_ms() - t1);   // host milliseconds spent ENQUEUEING the fusion + raycast + ICP-map kernels
     return GPS_OK;
+}
+
+int gps_tsdf_process_frame_tracked_gated(const gps_tsdf_state* s, const int16_t* depth_mm, const gps_track_config* cfg,
+                                         gps_track_state* ts, void* scratch, int64_t scratch_bytes, gps_stream stream,
+                                         void (*before_fusion)(void*), void* user) {
+    int r;
+    if ((r = gps_tsdf_frame_track(s, depth_mm, cfg, ts, scratch, scratch_bytes, stream)) != GPS_OK) return r;
+    if (before_fusion) before_fusion(user);  // everything above only READ the volume; what follows modifies it
+    return gps_tsdf_frame_map(s, ts, 1, 0, stream);
 }
 
 }  // extern "C"

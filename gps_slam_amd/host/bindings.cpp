@@ -293,6 +293,90 @@ PYBIND11_MODULE(_host, m) {
         return imageMetrics(render, gt, depth ? *depth : torch::Tensor());
     }, py::arg("render"), py::arg("gt"), py::arg("depth") = py::none());
 
+    // ---- failure modes (ITMLibSettings::behaviourOnFailure, ITMTrackingState::TrackingResult) and what the engine does with a verdict
+    py::enum_<ITMLib::ITMLibSettings::FailureMode>(m, "FailureMode")
+        .value("FAILUREMODE_RELOCALISE", ITMLib::ITMLibSettings::FAILUREMODE_RELOCALISE)
+        .value("FAILUREMODE_IGNORE", ITMLib::ITMLibSettings::FAILUREMODE_IGNORE)
+        .value("FAILUREMODE_STOP_INTEGRATION", ITMLib::ITMLibSettings::FAILUREMODE_STOP_INTEGRATION);
+    py::enum_<ITMTrackingState::TrackingResult>(m, "TrackingResult")
+        .value("TRACKING_GOOD", ITMTrackingState::TRACKING_GOOD)
+        .value("TRACKING_POOR", ITMTrackingState::TRACKING_POOR)
+        .value("TRACKING_FAILED", ITMTrackingState::TRACKING_FAILED);
+    m.def("failureModeFromString", &ITMLib::ITMLibSettings::failureModeFromString);
+    py::class_<ITMLib::FailureDecision>(m, "FailureDecision")
+        .def_readonly("result", &ITMLib::FailureDecision::result)
+        .def_readonly("useRelocaliser", &ITMLib::FailureDecision::useRelocaliser)
+        .def_readonly("harvest", &ITMLib::FailureDecision::harvest)
+        .def_readonly("relocalise", &ITMLib::FailureDecision::relocalise)
+        .def_readonly("fuse", &ITMLib::FailureDecision::fuse)
+        .def_readonly("refreshAndRaycast", &ITMLib::FailureDecision::refreshAndRaycast)
+        .def_readonly("relocalisationCount", &ITMLib::FailureDecision::relocalisationCount);
+    m.def("decideOnTrackingResult", &ITMLib::decideOnTrackingResult, py::arg("mode"), py::arg("trackerVerdict"), py::arg("addedKeyframe"),
+          py::arg("relocalisationCount"), py::arg("trackingInitialised"), py::arg("fusionActive"), py::arg("relocalised") = false);
+    py::class_<ITMLib::PoseQualityThresholds>(m, "PoseQualityThresholds")
+        .def(py::init<>())
+        .def_readwrite("enabled", &ITMLib::PoseQualityThresholds::enabled)
+        .def_readwrite("poorScore", &ITMLib::PoseQualityThresholds::poorScore)
+        .def_readwrite("poorInlierShare", &ITMLib::PoseQualityThresholds::poorInlierShare)
+        .def_readwrite("failedScore", &ITMLib::PoseQualityThresholds::failedScore)
+        .def_readwrite("failedInlierShare", &ITMLib::PoseQualityThresholds::failedInlierShare);
+    m.def("poseQualityVerdict", &ITMLib::poseQualityVerdict, py::arg("thresholds"), py::arg("score"), py::arg("inlierShare"));
+    // ---- FernRelocLib::Relocaliser<float> over the device relocaliser (host/relocaliser.hpp); frames on the current stream
+    py::class_<FernRelocLib::Relocaliser<float>>(m, "Relocaliser")
+        .def(py::init<int, int, float, float, float, int, int, int, uint64_t>(), py::arg("width"), py::arg("height"), py::arg("rangeMin"),
+             py::arg("rangeMax"), py::arg("harvestingThreshold") = 0.2f, py::arg("numFerns") = 500, py::arg("numDecisionsPerFern") = 4,
+             py::arg("capacity") = 4096, py::arg("seed") = 0)
+        .def("ProcessFrame", [](FernRelocLib::Relocaliser<float>& r, const torch::Tensor& depth, const torch::Tensor& pose, int sceneId, int k,
+                                bool harvest) {
+            TORCH_CHECK(depth.is_cuda() && depth.scalar_type() == torch::kFloat32 && depth.is_contiguous(), "depth must be a contiguous float32 device tensor");
+            auto p = pose.to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK(p.numel() == 32, "pose must be [2,16] (M, invM)");
+            r.ProcessFrame(depth.data_ptr<float>(), p.data_ptr<float>(), p.data_ptr<float>() + 16, sceneId, k, harvest, gpsh::current_stream());
+        }, py::arg("depth"), py::arg("pose"), py::arg("sceneId") = 0, py::arg("k") = 1, py::arg("harvestKeyframes") = true)
+        .def("ReadResult", [](FernRelocLib::Relocaliser<float>& r) {
+            const gps_reloc_result x = r.ReadResult(gpsh::current_stream());
+            py::dict d;
+            d["added_id"] = x.added_id; d["n_found"] = x.n_found; d["n_entries"] = x.n_entries; d["overflow"] = x.overflow;
+            d["ids"] = std::vector<int>(x.ids, x.ids + 4); d["distances"] = std::vector<float>(x.distances, x.distances + 4);
+            return d;
+        })
+        .def("RetrievePose", [](FernRelocLib::Relocaliser<float>& r, int id) {
+            const FernRelocLib::PoseInScene p = r.RetrievePose(id, gpsh::current_stream());
+            auto t = torch::empty({2, 16}, torch::kFloat32);
+            for (int i = 0; i < 16; i++) { t[0][i] = p.M[i]; t[1][i] = p.invM[i]; }
+            return std::make_pair(t, p.sceneIdx);
+        })
+        .def("numEntries", [](FernRelocLib::Relocaliser<float>& r) { return r.numEntries(gpsh::current_stream()); })
+        .def("SaveToDirectory", [](FernRelocLib::Relocaliser<float>& r, const std::string& d) { r.SaveToDirectory(d, gpsh::current_stream()); })
+        .def("LoadFromDirectory", [](FernRelocLib::Relocaliser<float>& r, const std::string& d) { r.LoadFromDirectory(d, gpsh::current_stream()); });
+    // the text formats alone, host code: read a database directory and write it again (both names end in '/')
+    m.def("relocDatabaseRewrite", [](const std::string& in, const std::string& out, int numFerns, int numDecisions, float threshold) {
+        const auto db = FernRelocLib::detail::readDatabase(in, numFerns, numDecisions, threshold);
+        FernRelocLib::detail::writeDatabase(db, out);
+        return db.totalEntries;
+    });
+    m.def("relocPoseFromParams", [](const std::vector<float>& p) {
+        TORCH_CHECK(p.size() == 6, "six SE3 parameters");
+        auto t = torch::empty({2, 16}, torch::kFloat32);
+        FernRelocLib::detail::poseFromParams(p.data(), t.data_ptr<float>(), t.data_ptr<float>() + 16);
+        return t;
+    });
+    m.def("relocParamsFromPose", [](const torch::Tensor& M) {
+        auto m_ = M.to(torch::kCPU, torch::kFloat32).contiguous();
+        TORCH_CHECK(m_.numel() >= 16, "M: 16 floats, ORUtils layout");
+        std::vector<float> p(6);
+        FernRelocLib::detail::paramsFromPose(m_.data_ptr<float>(), p.data());
+        return p;
+    });
+    m.def("tsdfConfigFailureMode", [](const gpsh::Node& tsdf_node) {
+        // the failure mode createTsdfEngine takes from a PIPE.TSDF node: the absent key is ignore, an unknown value throws
+        TsdfConfig t;
+        const gpsh::Config c = gpsh::flattenNode(tsdf_node, "PIPE.TSDF", [&](auto& v) { t.configFields(v); });
+        gpsh::ConfigReader reader{c};
+        t.configFields(reader);
+        return ITMLib::ITMLibSettings::failureModeFromString(t.failure_mode);
+    });
+
     // ---- TSDF engine
     py::class_<TsdfEngine>(m, "ITMBasicEngine")
         .def(py::init([](int w, int h, float fx, float fy, float cx, float cy, float voxel_size, float mu, float vmin,
@@ -326,6 +410,52 @@ PYBIND11_MODULE(_host, m) {
         .def("ProcessFrame", [](TsdfEngine& e, const torch::Tensor& rgb, const torch::Tensor& depth) {
             e.ProcessFrame(rgb, depth);
         })
+        .def("setFailureMode", &TsdfEngine::setFailureMode)
+        .def("failureMode", &TsdfEngine::failureMode)
+        .def("setPoseQualityThresholds", &TsdfEngine::setPoseQualityThresholds)
+        .def("forceTrackerResult", &TsdfEngine::forceTrackerResult, py::arg("frame"), py::arg("result"))
+        .def("clearForcedTrackerResults", &TsdfEngine::clearForcedTrackerResults)
+        .def("trackerResult", [](TsdfEngine& e) { return e.GetTrackingState()->trackerResult; })
+        .def("lastFrameFused", &TsdfEngine::lastFrameFused)
+        .def("inlierShare", [](TsdfEngine& e) {
+            // of the last TrackCamera: inliers of the last accepted evaluation over the valid depth pixels (0 before the first)
+            const int n = e.trackState().n_valid_max;
+            return n > 0 ? e.trackState().diag[8] / (float)n : 0.0f;
+        })
+        .def("hasRelocaliser", [](TsdfEngine& e) { return e.relocaliser() != nullptr; })
+        .def("relocaliserEntries", [](TsdfEngine& e) { return e.relocaliser() ? e.relocaliser()->numEntries(gpsh::current_stream()) : 0; })
+        .def("relocaliserPose", [](TsdfEngine& e, int id) {
+            TORCH_CHECK(e.relocaliser() != nullptr, "relocaliserPose: no relocaliser (failure mode is not relocalise, or no frame yet)");
+            const FernRelocLib::PoseInScene p = e.relocaliser()->RetrievePose(id, gpsh::current_stream());
+            auto t = torch::empty({2, 16}, torch::kFloat32);
+            for (int i = 0; i < 16; i++) { t[0][i] = p.M[i]; t[1][i] = p.invM[i]; }
+            return t;
+        })
+        .def("convertDepth", &TsdfEngine::convertDepth)
+        .def("relocaliseFromPose", [](TsdfEngine& e, const torch::Tensor& pose) {
+            auto p = pose.to(torch::kCPU, torch::kFloat32).contiguous();
+            TORCH_CHECK(p.numel() == 32, "relocaliseFromPose: pose must be [2,16] (M, invM)");
+            e.relocaliseFromPose(p.data_ptr<float>(), p.data_ptr<float>() + 16);
+            auto t = torch::empty({2, 16}, torch::kFloat32);
+            for (int i = 0; i < 16; i++) { t[0][i] = e.trackState().pose_M[i]; t[1][i] = e.trackState().pose_invM[i]; }
+            return t;
+        })
+        .def("visibleIds", [](TsdfEngine& e) {
+            // the live visible list: hash-slot ids of the blocks the last frame saw (host-synchronous; tests)
+            auto c = e.counters().cpu();
+            const int n = c.data_ptr<int32_t>()[GPS_TSDF_N_VISIBLE];
+            return torch::from_blob(e.state().visible_ids, {n}, torch::TensorOptions().dtype(torch::kInt32).device(e.counters().device())).clone();
+        })
+        .def("allocatedSlots", [](TsdfEngine& e) {
+            // hash-slot ids that hold an allocated block (ptr >= 0), ascending (host-synchronous; tests)
+            const int64_t n_total = (int64_t)e.state().n_buckets + e.state().n_excess;
+            auto h = torch::from_blob(e.state().hash, {n_total, 4}, torch::TensorOptions().dtype(torch::kInt32).device(e.counters().device()));
+            return torch::nonzero(h.select(1, 3) >= 0).reshape({-1}).to(torch::kInt32);
+        })
+        .def_readwrite("trackingInitialised", &TsdfEngine::trackingInitialised)
+        .def_readonly("relocalisationCount", &TsdfEngine::relocalisationCount)
+        .def_readonly("framesSeen", &TsdfEngine::framesSeen)
+        .def_readonly("lastRelocalisedTo", &TsdfEngine::lastRelocalisedTo)
         .def("runRaycastC2w", [](TsdfEngine& e, const torch::Tensor& c2w) {
             ORUtils::SE3Pose pose;
             auto c = c2w.to(torch::kCPU, torch::kFloat32).contiguous();

@@ -234,8 +234,10 @@ CLIEngine* createTsdfEngine(const DatasetReader& data_reader, const Config& conf
     internalSettings->noTotalEntries_blocks = tsdf.sdf_local_block_num;
     internalSettings->noBuckets = tsdf.sdf_bucket_num;
     internalSettings->excessListSize = tsdf.sdf_excess_list_size;
+    internalSettings->behaviourOnFailure = ITMLibSettings::failureModeFromString(tsdf.failure_mode);   // (an unknown name throws)
     ITMMainEngine* mainEngine =
         new ITMBasicEngine<ITMVoxel, ITMVoxelIndex>(internalSettings, rgbd_calib, rgb_images[0]->noDims, depth_images[0]->noDims);
+    dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine)->setFailureMode(internalSettings->behaviourOnFailure);
     if (tsdf.use_gt_pose) {
         auto* be = dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine);
         be->turnOffTracking();

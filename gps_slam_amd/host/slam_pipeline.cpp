@@ -681,7 +681,7 @@ void SLAMPipeline::processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb
     const double tt0 = now_ms();
     gate_wait_ms_ = handover_wait_ms_ = 0.0;
     // (with the tracker on the engine does not read them: kept for evalTrajectory)
-    if ((!main_engine->trackingActive || cam.c2w.defined()) && (int)main_engine->gtC2wPoses.size() <= main_engine->framesProcessed)
+    if ((!main_engine->trackingActive || cam.c2w.defined()) && (int)main_engine->gtC2wPoses.size() <= main_engine->framesSeen)
         main_engine->gtC2wPoses.push_back(cam.c2w);
     ITMTrackingState* ts;
     torch::Tensor frame_rgba;
@@ -710,6 +710,14 @@ void SLAMPipeline::processFrameImpl(int i, Camera& cam, const torch::Tensor& rgb
     for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) est.data_ptr<float>()[4 * r + c] = invM[4 * c + r];
     cam.c2w_slam = est;
+    if (!main_engine->lastFrameFused()) {
+        // a frame the engine did not fuse (failure modes: tracking lost, or the frames right after a relocalisation) adds nothing
+        // to the map: it is not offered as a keyframe and triggers no update.  Its camera still has the engine's pose.
+        if (frame_rgba.defined()) tsdf_engine->markConsumed();
+        stats.frames++;
+        times.per_frame += now_ms() - tt0;
+        return;
+    }
     // `curr_cam = cams[i]; curr_cam.toGPU();` (:83-84): a COPY of the caller's camera goes to the device -- the caller's keeps the
     // pose and no device tensors, so a frame's 12-byte-per-pixel image lives exactly as long as the pipeline's lists hold it
     // (held by the caller's camera it stayed for the whole run: 3.7 MB per frame at 640x480, i.e. a fresh 20 MB hipMalloc by the

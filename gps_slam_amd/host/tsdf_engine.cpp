@@ -73,6 +73,8 @@ TsdfEngine::TsdfEngine(int width, int height, float fx, float fy, float cx, floa
 void TsdfEngine::resetAll() {
     check(gps_tsdf_reset(&state_, current_stream()), "gps_tsdf_reset");
     framesProcessed = 0;
+    framesSeen = 0; relocalisationCount = 0; lastRelocalisedTo = -1; trackingInitialised = false; last_frame_fused_ = true;
+    relocaliser_.reset();
     tracked_frames_ = evals_total_ = rode_total_ = used_total_ = 0;
     camPoses.clear();
     camIntrincs.clear();
@@ -112,6 +114,8 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         frame_inputs_ = {rgb_u8, depth_mm_i16};  // keep alive while kernels may read them
         state_.rgb = ptr<uint8_t>(rgb_u8);
     }
+    if (behaviourOnFailure != ITMLib::ITMLibSettings::FAILUREMODE_IGNORE) return processFrameWithFailureModes(depth_mm_i16);
+    framesSeen++;
     if (trackingActive) {
         if (!track_scratch_.defined()) turnOnTracking();  // ITMLibSettings defaults
         std::function<void()> gate;
@@ -140,13 +144,119 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
     return &tracking_state_;
 }
 
+// the verdict of the last TrackCamera: GOOD unless thresholds are set (tsdf_engine.hpp, PoseQualityThresholds)
+ITMTrackingState::TrackingResult TsdfEngine::verdictOfLastTrack() const {
+    const int n_max = track_state_.n_valid_max;
+    return ITMLib::poseQualityVerdict(pose_quality_, track_state_.diag[10], n_max > 0 ? track_state_.diag[8] / (float)n_max : 0.0f);
+}
+
+void TsdfEngine::ensureRelocaliser() {   // ITMBasicEngine.tpp:57-60
+    if (!relocaliser_)
+        relocaliser_.reset(new FernRelocLib::Relocaliser<float>(state_.width, state_.height, state_.view_frustum_min,
+                                                               state_.view_frustum_max, 0.2f, 500, 4));
+}
+
+void TsdfEngine::convertDepth(const torch::Tensor& depth_mm_i16) {
+    TORCH_CHECK(depth_mm_i16.is_cuda() && depth_mm_i16.scalar_type() == torch::kInt16 && depth_mm_i16.is_contiguous() &&
+                    depth_mm_i16.numel() == (int64_t)state_.width * state_.height, "depth must be a contiguous int16 [H,W] device tensor");
+    check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), current_stream()), "gps_tsdf_convert_depth");
+}
+
+// ITMBasicEngine.tpp:325-329: pose := the keyframe's; UpdateVisibleList(..., resetVisibleList = true) + Prepare there; TrackCamera
+void TsdfEngine::relocaliseFromPose(const float* M, const float* invM) {
+    TORCH_CHECK(track_scratch_.defined(), "relocaliseFromPose: tracking has not been turned on");
+    const gps_stream st = current_stream();
+    float m[16], im[16];   // (M / invM may point into the tracking state)
+    memcpy(m, M, 64); memcpy(im, invM, 64);
+    memcpy(track_state_.pose_M, m, 64); memcpy(track_state_.pose_invM, im, 64);
+    check(gps_tsdf_frame_map(&state_, &track_state_, 0, 1, st), "gps_tsdf_frame_map");
+    check(gps_tsdf_track_camera(&state_, &track_cfg_, &track_state_, track_scratch_.data_ptr(), track_scratch_.numel(), st),
+          "gps_tsdf_track_camera");
+    pose_d_.SetBoth(track_state_.pose_M, track_state_.pose_invM);
+}
+
+// ITMBasicEngine::ProcessFrame with behaviourOnFailure != IGNORE (ITMBasicEngine.tpp:272-385)
+ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& depth_mm_i16) {
+    using TS = ITMTrackingState;
+    const gps_stream st = current_stream();
+    gps_track_state& ts = track_state_;
+    float oldM[16], oldInvM[16];
+    memcpy(oldM, ts.pose_M, 64); memcpy(oldInvM, ts.pose_invM, 64);
+    // tracking (:272-280)
+    TS::TrackingResult verdict = TS::TRACKING_GOOD;
+    if (trackingActive) {
+        if (!track_scratch_.defined()) turnOnTracking();
+        const bool tracks = ts.age_point_cloud != -1;
+        check(gps_tsdf_frame_track(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &ts, track_scratch_.data_ptr(),
+                                   track_scratch_.numel(), st), "gps_tsdf_frame_track");
+        if (tracks) {
+            verdict = verdictOfLastTrack();
+            tracked_frames_++;
+            for (int l = 0; l < 8; l++) evals_total_ += (int64_t)ts.diag[l];
+            rode_total_ += (int64_t)ts.diag[12]; used_total_ += (int64_t)ts.diag[13];
+        }
+    } else {
+        TORCH_CHECK((int)gtC2wPoses.size() > framesSeen, "gtC2wPoses must hold the pose of frame ", framesSeen);
+        auto c2w = gtC2wPoses[framesSeen].to(torch::kCPU, torch::kFloat32).contiguous();
+        pose_d_.SetInvM(c2w.data_ptr<float>());
+        memcpy(ts.pose_M, pose_d_.GetM(), 64); memcpy(ts.pose_invM, pose_d_.GetInvM(), 64);
+        check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), st), "gps_tsdf_convert_depth");
+    }
+    const auto forced = forced_results_.find(framesSeen);
+    if (forced != forced_results_.end()) verdict = forced->second;
+    framesSeen++;
+    // verdict mapping, relocaliser, relocalisation (:286-333)
+    auto d = ITMLib::decideOnTrackingResult(behaviourOnFailure, verdict, false, relocalisationCount, trackingInitialised, fusionActive);
+    if (d.useRelocaliser) {
+        ensureRelocaliser();
+        relocaliser_->ProcessFrame(state_.depth, ts.pose_M, ts.pose_invM, 0, 1, d.harvest, st);
+        if (d.relocalise) {
+            const gps_reloc_result r = relocaliser_->ReadResult(st);   // the one read-back, on a failed frame only
+            if (r.ids[0] >= 0 && trackingActive) {
+                const FernRelocLib::PoseInScene kf = relocaliser_->RetrievePose(r.ids[0], st);
+                lastRelocalisedTo = r.ids[0];
+                relocaliseFromPose(kf.M, kf.invM);
+                verdict = verdictOfLastTrack();
+            }
+            // (an empty database has no pose to restart from: the frame stays FAILED)
+            d = ITMLib::decideOnTrackingResult(behaviourOnFailure, verdict, false, d.relocalisationCount, trackingInitialised,
+                                               fusionActive, true);
+        }
+    }
+    relocalisationCount = d.relocalisationCount;
+    // fusion, or the visible list without allocation; the raycast for the next frame (:337-366)
+    last_frame_fused_ = d.fuse;
+    if (d.fuse) {
+        if (beforeNextFusion) { std::function<void()> gate; gate.swap(beforeNextFusion); gate(); }
+        if (framesProcessed > 50) trackingInitialised = true;
+        framesProcessed++;
+    }
+    if (d.refreshAndRaycast) {
+        // (a frame that does not fuse runs the visible-list refresh and the live raycast WITHOUT the beforeNextFusion gate: they
+        // write the live render state only -- visible_type / visible_ids, the live min/max and raycast images -- and the free-view
+        // raycasts of a map update have scratch, lists and counters of their own.  That holds as long as nothing on the map
+        // stream reads the live render state.)
+        check(gps_tsdf_frame_map(&state_, &ts, d.fuse ? 1 : 0, 0, st), "gps_tsdf_frame_map");
+    } else {
+        // (the table has one more row, fusion WITHOUT a raycast for a FAILED result before tracking is initialised; this engine
+        // cannot reach it: FAILED survives the verdict mapping only in RELOCALISE mode, where the count is 10 by then)
+        TORCH_CHECK(!d.fuse, "failure modes: fusion without a raycast");
+        memcpy(ts.pose_M, oldM, 64); memcpy(ts.pose_invM, oldInvM, 64);
+    }
+    pose_d_.SetBoth(ts.pose_M, ts.pose_invM);
+    tracking_state_.trackerResult = d.result;
+    camPoses.push_back(pose_d_);
+    camIntrincs.push_back(intrinsics_d);
+    return &tracking_state_;
+}
+
 ITMTrackingState* TsdfEngine::ProcessFrame(ITMUChar4Image* rgbImage, ITMShortImage* rawDepthImage) {
     TORCH_CHECK(rgbImage && rawDepthImage, "ProcessFrame: null image");
     TORCH_CHECK(rgbImage->noDims.x == state_.width && rgbImage->noDims.y == state_.height &&
                     rawDepthImage->noDims.x == state_.width && rawDepthImage->noDims.y == state_.height,
                 "ProcessFrame: image size differs from the engine's");
     const int64_t P = (int64_t)state_.width * state_.height;
-    const int slot = framesProcessed & 1;
+    const int slot = framesSeen & 1;
     auto on_device = [&](const torch::Tensor& dev, const torch::Tensor& host, torch::Tensor& stage, int64_t bytes) {
         if (dev.defined()) return dev;
         TORCH_CHECK(host.defined(), "ProcessFrame: image has neither a host nor a device copy");
@@ -336,6 +446,7 @@ void read_block(const std::string& path, torch::Tensor& dev, size_t elem_bytes) 
 void TsdfEngine::SaveToFile(const std::string& saveOutputDirectory) {
     const std::string d = with_slash(saveOutputDirectory), sc = d + "Scene/";
     mkdir(d.c_str(), 0755); mkdir((d + "Relocaliser/").c_str(), 0755); mkdir(sc.c_str(), 0755);
+    if (relocaliser_) relocaliser_->SaveToDirectory(d + "Relocaliser/", current_stream());   // ITMBasicEngine.tpp:125-132
     auto c = counters_.cpu();
     const int32_t* ch = c.data_ptr<int32_t>();
     write_block(sc + "voxel.dat", vba_, 8);
@@ -362,4 +473,10 @@ void TsdfEngine::LoadFromFile(const std::string& saveInputDirectory) {
     c.data_ptr<int32_t>()[GPS_TSDF_LAST_FREE_EXCESS] = last_excess;
     counters_.copy_(c);
     check(gps_tsdf_rebuild_index(&state_, current_stream()), "gps_tsdf_rebuild_index");  // the table was written from outside
+    // ITMBasicEngine.tpp:139-146: the relocaliser's database, when the directory holds one and this engine relocalises
+    const std::string rl = with_slash(saveInputDirectory) + "Relocaliser/";
+    if (behaviourOnFailure == ITMLib::ITMLibSettings::FAILUREMODE_RELOCALISE && std::ifstream((rl + "frames.txt").c_str())) {
+        ensureRelocaliser();
+        relocaliser_->LoadFromDirectory(rl, current_stream());
+    }
 }

@@ -19,8 +19,11 @@
 #include <functional>
 #include <mutex>
 
+#include <map>
+
 #include "gps_host_common.hpp"
 #include "geom_eval.hpp"
+#include "relocaliser.hpp"
 
 enum MemoryDeviceType { MEMORYDEVICE_CPU, MEMORYDEVICE_CUDA };
 
@@ -131,7 +134,75 @@ public:
     ITMSceneParams sceneParams;
     // hash table / voxel block array capacities (ITMVoxelBlockHash.h:18-22; runtime parameters here)
     int noTotalEntries_blocks = 0x40000, noBuckets = 0x100000, excessListSize = 0x20000;
+    // ITMLibSettings.h:24-29; the default is the reference's (ITMLibSettings.cpp:42)
+    enum FailureMode { FAILUREMODE_RELOCALISE, FAILUREMODE_IGNORE, FAILUREMODE_STOP_INTEGRATION };
+    FailureMode behaviourOnFailure = FAILUREMODE_IGNORE;
+    // TSDF.failure_mode of the configs: ignore | stop_integration | relocalise (anything else throws)
+    static FailureMode failureModeFromString(const std::string& name) {
+        if (name == "ignore") return FAILUREMODE_IGNORE;
+        if (name == "stop_integration") return FAILUREMODE_STOP_INTEGRATION;
+        if (name == "relocalise") return FAILUREMODE_RELOCALISE;
+        throw std::invalid_argument("failure_mode: '" + name + "' is not one of ignore, stop_integration, relocalise");
+    }
 };
+
+// What ITMBasicEngine::ProcessFrame does with a tracking verdict (ITMBasicEngine.tpp:286-366), as one pure function.
+//   trackerVerdict       trackingState->trackerResult of the frame's TrackCamera
+//   addedKeyframe        the relocaliser harvested this frame (known without asking it whenever it matters: a frame is only
+//                        offered for harvesting when its verdict is GOOD, and only relocalised when it is FAILED)
+//   relocalised          false: the evaluation after the frame's first TrackCamera.  true: the evaluation after the second
+//                        TrackCamera of a frame that relocalised (:329-331) -- the relocaliser stage is over, count is the 10 it set
+// -> result              the verdict the engine acts on and returns (:286-300)
+//    useRelocaliser      the frame goes through Relocaliser::ProcessFrame (:304-314), with `harvest` as harvestKeyframes
+//    relocalise          restart from the nearest keyframe's pose: rebuild the visible list, raycast, track again (:317-332), then
+//                        evaluate again with relocalised = true
+//    fuse                ITMDenseMapper::ProcessFrame (:338-347)
+//    refreshAndRaycast   UpdateVisibleList when the frame did not fuse, then Prepare (:349-364); false: the old pose comes back (:366)
+//    relocalisationCount the counter afterwards
+struct FailureDecision {
+    ITMTrackingState::TrackingResult result;
+    bool useRelocaliser, harvest, relocalise, fuse, refreshAndRaycast;
+    int relocalisationCount;
+};
+inline FailureDecision decideOnTrackingResult(ITMLibSettings::FailureMode mode, ITMTrackingState::TrackingResult trackerVerdict,
+                                              bool addedKeyframe, int relocalisationCount, bool trackingInitialised, bool fusionActive,
+                                              bool relocalised = false) {
+    FailureDecision d{ITMTrackingState::TRACKING_GOOD, false, false, false, false, false, relocalisationCount};
+    if (mode == ITMLibSettings::FAILUREMODE_RELOCALISE) d.result = trackerVerdict;
+    else if (mode == ITMLibSettings::FAILUREMODE_STOP_INTEGRATION)
+        d.result = trackerVerdict != ITMTrackingState::TRACKING_FAILED ? trackerVerdict : ITMTrackingState::TRACKING_POOR;
+    if (mode == ITMLibSettings::FAILUREMODE_RELOCALISE && !relocalised) {
+        if (d.result == ITMTrackingState::TRACKING_GOOD && d.relocalisationCount > 0) d.relocalisationCount--;
+        d.useRelocaliser = true;
+        d.harvest = d.result == ITMTrackingState::TRACKING_GOOD && d.relocalisationCount == 0;
+        if (!addedKeyframe && d.result == ITMTrackingState::TRACKING_FAILED) {
+            d.relocalise = true;
+            d.relocalisationCount = 10;
+            return d;   // the tail is decided by the second TrackCamera's verdict
+        }
+    }
+    d.fuse = (d.result == ITMTrackingState::TRACKING_GOOD || !trackingInitialised) && fusionActive && d.relocalisationCount == 0;
+    d.refreshAndRaycast = d.result == ITMTrackingState::TRACKING_GOOD || d.result == ITMTrackingState::TRACKING_POOR;
+    return d;
+}
+
+// The verdict itself.  The reference's comes from an SVM over four tracker statistics whose weights are constants of its source
+// (ITMExtendedTracker::UpdatePoseQuality); they are not shipped here.  In their place: thresholds on the residual score the tracker
+// already reports -- two of the SVM's four inputs: the residual score (trackDiag(10): the root of the mean robust residual, the
+// space threshold standing in for every outlier; larger is worse) and the inlier share (trackDiag(8) / n_valid_max: inliers of the
+// last accepted evaluation over the valid depth pixels; smaller is worse).  A POOR pair and a FAILED pair; either member of a
+// pair trips it.  Off by default so that the verdict stays GOOD, and no default values: nobody has measured where they sit.
+struct PoseQualityThresholds {
+    bool enabled = false;
+    float poorScore = 0.0f, poorInlierShare = 0.0f;       // score > poorScore or share < poorInlierShare: POOR
+    float failedScore = 0.0f, failedInlierShare = 0.0f;   // score > failedScore or share < failedInlierShare: FAILED
+};
+inline ITMTrackingState::TrackingResult poseQualityVerdict(const PoseQualityThresholds& t, float score, float inlierShare) {
+    if (!t.enabled) return ITMTrackingState::TRACKING_GOOD;
+    if (score > t.failedScore || inlierShare < t.failedInlierShare) return ITMTrackingState::TRACKING_FAILED;
+    if (score > t.poorScore || inlierShare < t.poorInlierShare) return ITMTrackingState::TRACKING_POOR;
+    return ITMTrackingState::TRACKING_GOOD;
+}
 
 class ITMIMUMeasurement;
 
@@ -209,6 +280,30 @@ public:
     // InfiniTAM_tools.cpp:59-62): poses then come from gtC2wPoses.  With tracking active (the reference's default) the
     // depth-only ExtendedTracker of ITMLibSettings.cpp:54-57 estimates them (gps_tsdf_process_frame_tracked).
     void turnOffTracking() { trackingActive = false; }
+
+    // ---- failure modes (ITMBasicEngine.tpp:286-366).  IGNORE, the default, is the path above, launch for launch: no relocaliser
+    // is created and verdicts, forced or not, are not looked at.  Otherwise a frame is frame_track, the verdict,
+    // decideOnTrackingResult, and what that says: the relocaliser (on the float depth image already in HBM; its answer is read
+    // back only on a frame that relocalises), fusion or the visible-list refresh without allocation, the raycast -- or, on
+    // FAILED, the old pose and the previous raycast.  framesProcessed then counts fused frames, as the reference's does; the
+    // frame index (gtC2wPoses, the staging slot, forced verdicts) is framesSeen.
+    void setFailureMode(ITMLib::ITMLibSettings::FailureMode m) { behaviourOnFailure = m; }
+    ITMLib::ITMLibSettings::FailureMode failureMode() const { return behaviourOnFailure; }
+    void setPoseQualityThresholds(const ITMLib::PoseQualityThresholds& t) { pose_quality_ = t; }
+    // the counterpart of the reference's ITMForceFailTracker: the verdict of the frame-th ProcessFrame call (0-based, since
+    // construction / resetAll) is `result`, whatever the tracker says
+    void forceTrackerResult(int frame, ITMTrackingState::TrackingResult result) { forced_results_[frame] = result; }
+    void clearForcedTrackerResults() { forced_results_.clear(); }
+    int relocalisationCount = 0;
+    int framesSeen = 0;              // ProcessFrame calls since construction / resetAll
+    int lastRelocalisedTo = -1;      // keyframe id the last relocalisation restarted from
+    bool trackingInitialised = false, fusionActive = true;
+    bool lastFrameFused() const { return last_frame_fused_; }
+    FernRelocLib::Relocaliser<float>* relocaliser() { return relocaliser_.get(); }
+    // the relocalisation step on its own (ITMBasicEngine.tpp:325-329): the pose becomes (M, invM), the visible list is rebuilt
+    // and the live raycast rendered there, and the tracker refines the pose against the depth image last converted
+    void relocaliseFromPose(const float* M, const float* invM);
+    void convertDepth(const torch::Tensor& depth_mm_i16);   // view building's depth conversion alone (ITMViewBuilder: mm -> metres)
     // the tracker's argument line through the BAR (default, when the device memory is host-visible) or in the pinned mailbox
     void setBarArgLine(bool on) { bar_arg_line = on; track_state_.dev_arg_line = on ? track_arg_line_.get() : nullptr; }
     bool usesBarArgLine() const { return track_state_.dev_arg_line != nullptr; }
@@ -286,6 +381,14 @@ private:
     static constexpr int kMaxRidingAlong = 3;
     int64_t tracked_frames_ = 0, evals_total_ = 0, rode_total_ = 0, used_total_ = 0;
     int poses_riding_along = 1;   // (0 / 1 / 2 measured on the 640x480 loop: 973 / 993 / 980 frames/s sequential, 1,316 / 1,324 / 1,306 overlap)
+    ITMLib::ITMLibSettings::FailureMode behaviourOnFailure = ITMLib::ITMLibSettings::FAILUREMODE_IGNORE;
+    ITMLib::PoseQualityThresholds pose_quality_;
+    std::map<int, ITMTrackingState::TrackingResult> forced_results_;
+    std::unique_ptr<FernRelocLib::Relocaliser<float>> relocaliser_;
+    bool last_frame_fused_ = true;
+    ITMTrackingState::TrackingResult verdictOfLastTrack() const;
+    void ensureRelocaliser();
+    ITMTrackingState* processFrameWithFailureModes(const torch::Tensor& depth_mm_i16);
     ORUtils::SE3Pose pose_d_;
     ITMTrackingState tracking_state_{&pose_d_};
     ITMUChar4Image free_image_;

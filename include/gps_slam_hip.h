@@ -65,7 +65,11 @@ GPS_API const char *gps_build_flags(void);
 #define GPS_TIMED_INTEGRATE 6
 #define GPS_TIMED_RAYCAST 7
 #define GPS_TIMED_EXPOSURE 8 /* the per-frame exposure kernels (gps_exposure_*, the train step's table reduce + Adam launch) */
-#define GPS_TIMED_KINDS 9
+#define GPS_TIMED_RELOC_PYRAMID 9   /* the relocaliser's four launches (gps_reloc_process_frame) */
+#define GPS_TIMED_RELOC_BLUR_CODE 10
+#define GPS_TIMED_RELOC_SEARCH 11
+#define GPS_TIMED_RELOC_FINISH 12
+#define GPS_TIMED_KINDS 13
 GPS_API int gps_launch_timing_start(int capacity);
 GPS_API int gps_launch_timing_stop(void);
 GPS_API int gps_launch_timing_read(int kind, double *total_us, int64_t *launches, double *total_us_flagged,
@@ -499,6 +503,71 @@ GPS_API int gps_image_metrics(int K, int H, int W, int dtype, const void *render
                               void *workspace, int64_t workspace_bytes, double *mse, double *ssim, int64_t *sse_u8,
                               gps_stream stream);
 
+/* ------------------------------------------------------------------ */
+/* Keyframe relocaliser: fern codes of depth frames, on the device     */
+/* ------------------------------------------------------------------ */
+
+/* InfiniTAM's FernRelocLib (Relocaliser.h:48-84) on the float depth image in HBM: four hole-aware 2x2 subsamples (PixelUtils.h:
+ * 168-199; floor sizes at every level, so the result is (width / 16) x (height / 16)), the separable hole-aware Gaussian at
+ * sigma 2.5 (17 taps, x then y), the fern code (num_ferns bytes, bit d of byte f = !(blurred[location] < threshold),
+ * FernConservatory.cpp:31-47), the k nearest stored codes (distance = (num_ferns - equal bytes) / num_ferns in float; among equal
+ * distances the LATER entry comes first, RelocDatabase.cpp:40-58; missing neighbours are id -1 at distance 1.0) and keyframe
+ * harvesting decided on the device (Relocaliser.h:72-78: when `harvest` is set and nothing was found or distances[0] >
+ * harvest_threshold, the code, the pose and the scene id are appended under the next id).  The blurred image, the code and every
+ * answer are bit-equal to the reference's for the same fern table.  A full database adds nothing: it raises the overflow counter
+ * and never writes past its arrays.
+ *
+ * gps_reloc_create allocates the state (device memory: the fern table, codes uint8[capacity, num_ferns], poses float[capacity, 32]
+ * = M then invM in ORUtils layout, scene ids, the entry count and the result record) and uploads a default fern table drawn by
+ * the library's own seeded generator with the reference's sampling rule (gps_reloc_default_ferns, host code: locations uniform in
+ * (width / 32) x (height / 32) -- the reference draws them there although the code reads the width / 16 image -- thresholds
+ * uniform in [range_min, range_max)).  Limits: width, height >= 32, (width / 16) * (height / 16) <= 4096, 1 <= num_decisions <= 7,
+ * capacity > 0.  gps_reloc_set_ferns replaces the table (xy: int32[count, 2], count == num_ferns * num_decisions, every location
+ * inside the width / 16 image; synchronises the stream).  A state belongs to ONE stream at a time: gps_reloc_set_ferns, gps_reloc_import and
+ * gps_reloc_set_debug_outputs only wait for the stream they are given, so a frame still in flight on another stream would read a
+ * half-replaced table or database.
+ *
+ * gps_reloc_process_frame is stream-ordered: four launches, no allocation, no host synchronisation; pose_M / pose_invM are HOST
+ * float[16] read during the call.  Its result stays on the device until gps_reloc_read_result (which synchronises the stream)
+ * copies it; a later frame overwrites it.  gps_reloc_retrieve_pose, gps_reloc_export (host arrays sized for max_entries; all
+ * three NULL: the count and the overflow counter alone; GPS_ERR_CAPACITY when the database holds more), gps_reloc_import (replaces
+ * the database, clears the overflow counter) and gps_reloc_check_guards (GPS_ERR_CAPACITY if the bytes directly behind one of the
+ * per-entry arrays changed) synchronise the stream too.  gps_reloc_set_debug_outputs: optional device arrays that every later
+ * frame also writes its blurred image (float[(height / 16) * (width / 16)]) and its code (uint8[num_ferns]) to (NULL: off).
+ * gps_reloc_info: {width, height, width / 16, height / 16, num_ferns, num_decisions, capacity, taps}.
+ * GPS_ERR_ARG, before any device work, for a NULL state or array, k outside 1..GPS_RELOC_MAX_K, a size outside the limits and
+ * a count that differs from the state's. */
+#define GPS_RELOC_MAX_K 4
+typedef struct gps_reloc_state gps_reloc_state;
+typedef struct {
+    int32_t added_id;                   /* id of the harvested keyframe, or -1 */
+    int32_t n_found;                    /* neighbours found (<= k) */
+    int32_t ids[GPS_RELOC_MAX_K];       /* nearest first; -1 beyond n_found and beyond k */
+    float distances[GPS_RELOC_MAX_K];   /* 1.0 where the id is -1 */
+    int32_t n_entries;                  /* entries after this frame */
+    int32_t overflow;                   /* harvests refused by a full database since creation / import */
+} gps_reloc_result;
+GPS_API int gps_reloc_gaussian_taps(float sigma, int max_taps, float *coeff, int *n_taps); /* createGaussianFilter, host code */
+GPS_API int gps_reloc_default_ferns(int width, int height, int num_ferns, int num_decisions, float range_min, float range_max,
+                                    uint64_t seed, int32_t *xy, float *thresholds);
+GPS_API int gps_reloc_create(gps_reloc_state **out, int width, int height, int num_ferns, int num_decisions, float range_min,
+                             float range_max, float harvest_threshold, int capacity, uint64_t seed);
+GPS_API int gps_reloc_destroy(gps_reloc_state *state);
+GPS_API int gps_reloc_info(const gps_reloc_state *state, int32_t *info8);
+GPS_API int gps_reloc_set_ferns(gps_reloc_state *state, const int32_t *xy, const float *thresholds, int count, gps_stream stream);
+GPS_API int gps_reloc_get_ferns(const gps_reloc_state *state, int32_t *xy, float *thresholds, int count);
+GPS_API int gps_reloc_set_debug_outputs(gps_reloc_state *state, float *blurred, uint8_t *code);
+GPS_API int gps_reloc_process_frame(gps_reloc_state *state, const float *depth_f32, const float *pose_M, const float *pose_invM,
+                                    int scene_id, int k, int harvest, gps_stream stream);
+GPS_API int gps_reloc_read_result(gps_reloc_state *state, gps_reloc_result *out, gps_stream stream);
+GPS_API int gps_reloc_retrieve_pose(gps_reloc_state *state, int id, float *pose_M, float *pose_invM, int32_t *scene_id,
+                                    gps_stream stream);
+GPS_API int gps_reloc_export(gps_reloc_state *state, int max_entries, uint8_t *codes, float *poses, int32_t *scene_ids,
+                             int32_t *n_entries, int32_t *overflow, gps_stream stream);
+GPS_API int gps_reloc_import(gps_reloc_state *state, int n_entries, const uint8_t *codes, const float *poses,
+                             const int32_t *scene_ids, gps_stream stream);
+GPS_API int gps_reloc_check_guards(gps_reloc_state *state, gps_stream stream);
+
 /* The sample mask of SLAMPipeline::initNewGaussians (slam/slam_pipeline.cpp:450-526) in one launch instead of ~12 tensor ops:
  *   valid = depth in (depth_vis_min, depth_vis_max) and vertex.sum(-1) != 0
  *   mask  = mean(|src_rgb - image|, -1) > color_error_thres  and  valid  [and alpha < alpha_vis_max, if alpha != NULL]
@@ -930,6 +999,9 @@ typedef struct {
      * gps_track_arg_line_alloc returns has room).  Same poses, bit for bit; fewer host <-> device round trips per frame
      * (diag[12] / diag[13] = poses that rode along / that the loop consumed).  Kept by gps_track_state_reset. */
     int32_t mailbox_bytes;
+    /* of the last TrackCamera: valid depth pixels at the finest level -- the n_max of UpdatePoseQuality, the denominator of the
+     * inlier share diag[8] / n_valid_max (0 before the first tracked frame) */
+    int32_t n_valid_max;
 } gps_track_state;
 
 /* Builds the configuration from the reference's tracker string parameters (ITMLibSettings.cpp:54-57 default:
@@ -984,6 +1056,20 @@ GPS_API int gps_tsdf_process_frame_tracked(const gps_tsdf_state *s, const int16_
 GPS_API int gps_tsdf_process_frame_tracked_gated(const gps_tsdf_state *s, const int16_t *depth_mm, const gps_track_config *cfg,
                                                  gps_track_state *ts, void *scratch, int64_t scratch_bytes, gps_stream stream,
                                                  void (*before_fusion)(void *user), void *user);
+
+/* The two halves of that frame on their own, for an engine that decides between them (failure modes, ITMBasicEngine.tpp:286-366):
+ * gps_tsdf_frame_track is the reading part (depth conversion, and tracking once a point cloud exists); gps_tsdf_frame_map is
+ * ITMDenseMapper::ProcessFrame (fuse != 0: allocate + integrate) or ITMDenseMapper::UpdateVisibleList (fuse == 0:
+ * gps_tsdf_update_visible_list), followed by ITMTrackingController::Prepare at ts->pose (expected depths, raycast, ICP maps).
+ * gps_tsdf_process_frame_tracked_gated is frame_track, the hook, frame_map(fuse = 1).
+ * gps_tsdf_update_visible_list: the allocation sweep of gps_tsdf_allocate with allocation suppressed (AllocateSceneFromDepth's
+ * onlyUpdateVisibleList) -- existing blocks inside the depth band are marked visible, last frame's visible blocks are re-tested
+ * against the frustum (reset_visible != 0: dropped instead), no block is allocated and no counter but N_VISIBLE changes. */
+GPS_API int gps_tsdf_update_visible_list(const gps_tsdf_state *s, const float *M, const float *invM, int reset_visible,
+                                         gps_stream stream);
+GPS_API int gps_tsdf_frame_track(const gps_tsdf_state *s, const int16_t *depth_mm, const gps_track_config *cfg, gps_track_state *ts,
+                                 void *scratch, int64_t scratch_bytes, gps_stream stream);
+GPS_API int gps_tsdf_frame_map(const gps_tsdf_state *s, gps_track_state *ts, int fuse, int reset_visible, gps_stream stream);
 
 #ifdef __cplusplus
 }
