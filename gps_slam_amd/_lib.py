@@ -145,6 +145,17 @@ PROTOTYPES = {
     "gps_tsdf_update_visible_list": (i32, [C.POINTER(TsdfState), vp, vp, i32, vp]),
     "gps_tsdf_frame_track": (i32, [C.POINTER(TsdfState), vp, C.POINTER(TrackConfig), C.POINTER(TrackState), vp, i64, vp]),
     "gps_tsdf_frame_map": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), i32, i32, vp]),
+    "gps_tsdf_forward_block_bytes": (i64, [i32, i32]),
+    "gps_tsdf_forward_project": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
+    "gps_tsdf_forward_fill": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
+    "gps_tsdf_forward_render": (i32, [C.POINTER(TsdfState), vp, vp, vp, vp]),
+    "gps_tsdf_forward_missing": (i32, [C.POINTER(TsdfState), vp, vp, vp, i32, vp]),
+    "gps_track_far_from_point_cloud": (i32, [C.POINTER(TrackState), vp]),
+    "gps_tsdf_prepare": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), vp, i32, vp]),
+    "gps_tsdf_frame_map_fwd": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), i32, i32, vp, i32, vp]),
+    "gps_tsdf_process_frame_fwd": (i32, [C.POINTER(TsdfState), vp, vp, vp, C.POINTER(TrackState), vp, i32, vp]),
+    "gps_tsdf_render_colour_from": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
+    "gps_tsdf_render_live": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), vp, vp, vp]),
     "gps_tsdf_convert_depth": (i32, [C.POINTER(TsdfState), vp, vp]),
     "gps_tsdf_allocate": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_integrate": (i32, [C.POINTER(TsdfState), vp, vp]),

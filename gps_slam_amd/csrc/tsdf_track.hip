@@ -1544,21 +1544,8 @@ int gps_tsdf_frame_track(const gps_tsdf_state* s, const int16_t* depth_mm, const
 }
 
 int gps_tsdf_frame_map(const gps_tsdf_state* s, gps_track_state* ts, int fuse, int reset_visible, gps_stream stream) {
-    GPS_REQUIRE(s && ts);
-    int r;
-    const double t1 = wall_ms();
-    if (fuse) {
-        if ((r = gps_tsdf_allocate(s, ts->pose_M, ts->pose_invM, stream)) != GPS_OK) return r;
-        if ((r = gps_tsdf_integrate(s, ts->pose_M, stream)) != GPS_OK) return r;
-    } else {
-        if ((r = gps_tsdf_update_visible_list(s, ts->pose_M, ts->pose_invM, reset_visible, stream)) != GPS_OK) return r;
-    }
-    if ((r = gps_tsdf_expected_depths_and_raycast(s, ts->pose_M, ts->pose_invM, 0, 1, stream)) != GPS_OK) return r;
-    if ((r = gps_tsdf_icp_maps(s, ts->pose_invM, stream)) != GPS_OK) return r;
-    memcpy(ts->pose_pc_M, ts->pose_M, 64);  // pose_pointCloud := pose_d (ITMTrackingController.h:87-93)
-    ts->age_point_cloud = (ts->age_point_cloud == -1) ? -2 : 0;
-    ts->diag[15] = (float)(wall_ms() - t1);   // host milliseconds spent ENQUEUEING the fusion + raycast + ICP-map kernels
-    return GPS_OK;
+    // (Prepare lives in tsdf_forward.hip: without a forward-render block it is the full cast + ICP maps + pose_pointCloud := pose_d)
+    return gps_tsdf_frame_map_fwd(s, ts, fuse, reset_visible, nullptr, 0, stream);
 }
 
 int gps_tsdf_process_frame_tracked_gated(const gps_tsdf_state* s, const int16_t* depth_mm, const gps_track_config* cfg,

@@ -376,6 +376,14 @@ PYBIND11_MODULE(_host, m) {
         t.configFields(reader);
         return ITMLib::ITMLibSettings::failureModeFromString(t.failure_mode);
     });
+    m.def("tsdfConfigUseApproximateRaycast", [](const gpsh::Node& tsdf_node) {
+        // what createTsdfEngine takes from a PIPE.TSDF node: the absent key is false, a misspelt key is an unknown key
+        TsdfConfig t;
+        const gpsh::Config c = gpsh::flattenNode(tsdf_node, "PIPE.TSDF", [&](auto& v) { t.configFields(v); });
+        gpsh::ConfigReader reader{c};
+        t.configFields(reader);
+        return t.use_approximate_raycast;
+    });
 
     // ---- TSDF engine
     py::class_<TsdfEngine>(m, "ITMBasicEngine")
@@ -465,6 +473,14 @@ PYBIND11_MODULE(_host, m) {
         .def("GetFreeImage", [](TsdfEngine& e) { return e.GetFreeImage()->tensor(); })
         .def("GetFreeVertex", [](TsdfEngine& e) { return e.GetFreeVertex()->tensor(); })
         .def("GetLiveVertex", [](TsdfEngine& e) { return e.GetLiveVertex()->tensor(); })
+        // ---- approximate raycast (ITMLibSettings::useApproximateRaycast) and the live re-render, runRaycast(NULL, NULL)
+        .def("setUseApproximateRaycast", &TsdfEngine::setUseApproximateRaycast)
+        .def("usesApproximateRaycast", &TsdfEngine::usesApproximateRaycast)
+        .def("agePointCloud", &TsdfEngine::agePointCloud)
+        .def("runRaycast", [](TsdfEngine& e) { e.runRaycast(nullptr, nullptr); })
+        .def("GetLiveImage", &TsdfEngine::GetLiveImage)
+        .def("GetForwardProjection", &TsdfEngine::GetForwardProjection)
+        .def("forwardMissingPoints", &TsdfEngine::forwardMissingPoints)
         .def("getVoxelSize", &TsdfEngine::getVoxelSize)
         .def("counters", &TsdfEngine::counters)
         .def("MeshScene", &TsdfEngine::MeshScene, py::arg("maxTriangles") = (int64_t)1 << 24)

@@ -238,6 +238,8 @@ CLIEngine* createTsdfEngine(const DatasetReader& data_reader, const Config& conf
     ITMMainEngine* mainEngine =
         new ITMBasicEngine<ITMVoxel, ITMVoxelIndex>(internalSettings, rgbd_calib, rgb_images[0]->noDims, depth_images[0]->noDims);
     dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine)->setFailureMode(internalSettings->behaviourOnFailure);
+    internalSettings->useApproximateRaycast = tsdf.use_approximate_raycast;
+    dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine)->setUseApproximateRaycast(internalSettings->useApproximateRaycast);
     if (tsdf.use_gt_pose) {
         auto* be = dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine);
         be->turnOffTracking();

@@ -120,11 +120,18 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         if (!track_scratch_.defined()) turnOnTracking();  // ITMLibSettings defaults
         std::function<void()> gate;
         gate.swap(beforeNextFusion);
-        check(gps_tsdf_process_frame_tracked_gated(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_,
-                                                   track_scratch_.data_ptr(), track_scratch_.numel(), current_stream(),
-                                                   gate ? +[](void* f) { (*static_cast<std::function<void()>*>(f))(); } : nullptr,
-                                                   gate ? &gate : nullptr),
-              "gps_tsdf_process_frame_tracked");
+        if (useApproximateRaycast) {   // the same two halves, Prepare with the forward render
+            check(gps_tsdf_frame_track(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_, track_scratch_.data_ptr(),
+                                       track_scratch_.numel(), current_stream()), "gps_tsdf_frame_track");
+            if (gate) gate();
+            check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 1, 0, forwardBlock(), 1, current_stream()), "gps_tsdf_frame_map_fwd");
+        } else {
+            check(gps_tsdf_process_frame_tracked_gated(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_,
+                                                       track_scratch_.data_ptr(), track_scratch_.numel(), current_stream(),
+                                                       gate ? +[](void* f) { (*static_cast<std::function<void()>*>(f))(); } : nullptr,
+                                                       gate ? &gate : nullptr),
+                  "gps_tsdf_process_frame_tracked");
+        }
         pose_d_.SetBoth(track_state_.pose_M, track_state_.pose_invM);
         tracked_frames_++;
         for (int l = 0; l < 8; l++) evals_total_ += (int64_t)track_state_.diag[l];
@@ -135,8 +142,10 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         pose_d_.SetInvM(c2w.data_ptr<float>());
         pose_d_.Coerce();
         if (beforeNextFusion) { std::function<void()> gate; gate.swap(beforeNextFusion); gate(); }
-        check(gps_tsdf_process_frame(&state_, ptr<int16_t>(depth_mm_i16), pose_d_.GetM(), pose_d_.GetInvM(),
-                                     current_stream()), "gps_tsdf_process_frame");
+        // (gps_tsdf_process_frame's launches; Prepare runs with tracking off too -- ITMBasicEngine.tpp:355 -- and keeps the point
+        // cloud's age and pose in the tracking state)
+        check(gps_tsdf_process_frame_fwd(&state_, ptr<int16_t>(depth_mm_i16), pose_d_.GetM(), pose_d_.GetInvM(), &track_state_,
+                                         forwardBlock(), useApproximateRaycast ? 1 : 0, current_stream()), "gps_tsdf_process_frame_fwd");
     }
     camPoses.push_back(pose_d_);
     camIntrincs.push_back(intrinsics_d);
@@ -169,7 +178,7 @@ void TsdfEngine::relocaliseFromPose(const float* M, const float* invM) {
     float m[16], im[16];   // (M / invM may point into the tracking state)
     memcpy(m, M, 64); memcpy(im, invM, 64);
     memcpy(track_state_.pose_M, m, 64); memcpy(track_state_.pose_invM, im, 64);
-    check(gps_tsdf_frame_map(&state_, &track_state_, 0, 1, st), "gps_tsdf_frame_map");
+    check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 0, 1, forwardBlock(), useApproximateRaycast ? 1 : 0, st), "gps_tsdf_frame_map_fwd");
     check(gps_tsdf_track_camera(&state_, &track_cfg_, &track_state_, track_scratch_.data_ptr(), track_scratch_.numel(), st),
           "gps_tsdf_track_camera");
     pose_d_.SetBoth(track_state_.pose_M, track_state_.pose_invM);
@@ -236,7 +245,8 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
         // write the live render state only -- visible_type / visible_ids, the live min/max and raycast images -- and the free-view
         // raycasts of a map update have scratch, lists and counters of their own.  That holds as long as nothing on the map
         // stream reads the live render state.)
-        check(gps_tsdf_frame_map(&state_, &ts, d.fuse ? 1 : 0, 0, st), "gps_tsdf_frame_map");
+        check(gps_tsdf_frame_map_fwd(&state_, &ts, d.fuse ? 1 : 0, 0, forwardBlock(), useApproximateRaycast ? 1 : 0, st),
+              "gps_tsdf_frame_map_fwd");
     } else {
         // (the table has one more row, fusion WITHOUT a raycast for a FAILED result before tracking is initialised; this engine
         // cannot reach it: FAILED survives the verdict mapping only in RELOCALISE mode, where the count is 10 by then)
@@ -272,8 +282,14 @@ ITMTrackingState* TsdfEngine::ProcessFrame(ITMUChar4Image* rgbImage, ITMShortIma
 }
 
 void TsdfEngine::runRaycast(ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics) {
-    TORCH_CHECK(pose != nullptr, "runRaycast(NULL, NULL) (re-render of the live view, ITMBasicEngine.tpp:503-518) is not on "
-                "SLAMPipeline's path and is not implemented; pass the pose of the view");
+    if (pose == nullptr && intrinsics == nullptr) {   // the live view again (ITMBasicEngine.tpp:503-518)
+        if (framesSeen == 0) return;   // (view == NULL)
+        if (!live_colour_.defined()) live_colour_ = zeros_bytes((int64_t)state_.width * state_.height * 4, device_).view({state_.height, state_.width, 4});
+        check(gps_tsdf_render_live(&state_, &track_state_, fwd_block_.defined() ? fwd_block_.data_ptr() : nullptr,
+                                   ptr<uint8_t>(live_colour_), current_stream()), "gps_tsdf_render_live");
+        return;
+    }
+    TORCH_CHECK(pose != nullptr, "runRaycast: intrinsics without a pose");
     gps_tsdf_state s;
     { std::lock_guard<std::mutex> lk(state_mu_); s = state_; }
     if (intrinsics) {
@@ -283,6 +299,28 @@ void TsdfEngine::runRaycast(ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intri
         s.cx = intrinsics->projectionParamsSimple.px; s.cy = intrinsics->projectionParamsSimple.py;
     }
     check(gps_tsdf_free_raycast(&s, pose->GetM(), pose->GetInvM(), current_stream()), "gps_tsdf_free_raycast");
+}
+
+void* TsdfEngine::forwardBlock() {
+    if (!useApproximateRaycast) return nullptr;
+    if (!fwd_block_.defined()) fwd_block_ = zeros_bytes(gps_tsdf_forward_block_bytes(state_.width, state_.height), device_);
+    return fwd_block_.data_ptr();
+}
+
+torch::Tensor TsdfEngine::GetForwardProjection() const {
+    if (!fwd_block_.defined()) return torch::Tensor();
+    const int64_t P = (int64_t)state_.width * state_.height;
+    return fwd_block_.slice(0, 0, P * 16).view(torch::kFloat32).view({state_.height, state_.width, 4});
+}
+
+std::pair<int, torch::Tensor> TsdfEngine::forwardMissingPoints() const {
+    TORCH_CHECK(fwd_block_.defined(), "forwardMissingPoints: no forward render yet");
+    const int P = state_.width * state_.height;
+    auto list = torch::zeros({P}, torch::kInt32);
+    int32_t n = 0;
+    check(gps_tsdf_forward_missing(&state_, fwd_block_.data_ptr(), &n, list.data_ptr<int32_t>(), P, current_stream()),
+          "gps_tsdf_forward_missing");
+    return {n, list.slice(0, 0, n)};
 }
 
 // view k's render state, created (and initialised: gps_tsdf_view_init) on first use

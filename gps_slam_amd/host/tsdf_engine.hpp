@@ -137,6 +137,8 @@ public:
     // ITMLibSettings.h:24-29; the default is the reference's (ITMLibSettings.cpp:42)
     enum FailureMode { FAILUREMODE_RELOCALISE, FAILUREMODE_IGNORE, FAILUREMODE_STOP_INTEGRATION };
     FailureMode behaviourOnFailure = FAILUREMODE_IGNORE;
+    // ITMLibSettings.h:45; the default is the reference's (ITMLibSettings.cpp:36).  TSDF.use_approximate_raycast of the configs.
+    bool useApproximateRaycast = false;
     // TSDF.failure_mode of the configs: ignore | stop_integration | relocalise (anything else throws)
     static FailureMode failureModeFromString(const std::string& name) {
         if (name == "ignore") return FAILUREMODE_IGNORE;
@@ -227,7 +229,8 @@ public:
     ITMTrackingState* ProcessFrame(const torch::Tensor& rgb_u8, const torch::Tensor& depth_mm_i16);
     // ITMBasicEngine::runRaycast(pose, intrinsics) (ITMBasicEngine.tpp:501-526): free-view FindVisibleBlocks +
     // CreateExpectedDepths + RenderImage into the free-view render state.  intrinsics == NULL: the depth camera's.
-    // (pose == NULL && intrinsics == NULL -- re-render of the live view, :503-518 -- is not on SLAMPipeline's path: throws.)
+    // pose == NULL && intrinsics == NULL: the re-render of the live view (:503-518) in colour from the volume, from the last
+    // full cast while it is current (age_pointCloud <= 0), from the forward projection afterwards -> GetLiveImage().
     void runRaycast(ORUtils::SE3Pose* pose = nullptr, ITMLib::ITMIntrinsics* intrinsics = nullptr);
     // ITMViewBuilder::UpdateView (ViewBuilding/CUDA/ITMViewBuilder_CUDA.cu:32-91) + ProcessFrame: images with a host copy only
     // are uploaded (asynchronously, pinned -> the engine's staging buffers) on the current stream first; images with a device
@@ -249,6 +252,16 @@ public:
     ITMUChar4Image* GetFreeImage() { return &free_image_; }
     ITMFloat4Image* GetFreeVertex() { return &free_vertex_; }
     ITMFloat4Image* GetLiveVertex() { return &live_vertex_; }
+    // ---- approximate raycast (ITMLibSettings::useApproximateRaycast; gps_tsdf_prepare): while the camera stays within
+    // sqrt(0.0005) m of the last full cast and that cast is at most 5 frames old, Prepare forward-projects it into the new pose
+    // and casts rays for the empty pixels only; the tracker keeps aligning against the ICP maps of the full cast.
+    void setUseApproximateRaycast(bool on) { useApproximateRaycast = on; }
+    bool usesApproximateRaycast() const { return useApproximateRaycast; }
+    int agePointCloud() const { return track_state_.age_point_cloud; }
+    torch::Tensor GetForwardProjection() const;   // renderState->forwardProjection, float [H,W,4] (undefined before the first use)
+    torch::Tensor GetLiveImage() const { return live_colour_; }   // uchar4 [H,W,4] of the last runRaycast(NULL, NULL)
+    // (noFwdProjMissingPoints, the list) of the last forward render: blocking read-back, tests / statistics only
+    std::pair<int, torch::Tensor> forwardMissingPoints() const;
     float getVoxelSize() const { return state_.voxel_size; }
     ITMTrackingState* GetTrackingState() { return &tracking_state_; }
 
@@ -386,6 +399,9 @@ private:
     std::map<int, ITMTrackingState::TrackingResult> forced_results_;
     std::unique_ptr<FernRelocLib::Relocaliser<float>> relocaliser_;
     bool last_frame_fused_ = true;
+    bool useApproximateRaycast = false;
+    torch::Tensor fwd_block_, live_colour_;
+    void* forwardBlock();   // the forward-render block when the option is on (allocated on first use), else NULL
     ITMTrackingState::TrackingResult verdictOfLastTrack() const;
     void ensureRelocaliser();
     ITMTrackingState* processFrameWithFailureModes(const torch::Tensor& depth_mm_i16);

@@ -45,8 +45,12 @@ class TsdfEngine:
 
     def __init__(self, width, height, fx, fy, cx, cy, voxel_size=0.005, mu=0.02, view_frustum_min=0.2,
                  view_frustum_max=10.0, n_blocks=SDF_LOCAL_BLOCK_NUM, n_buckets=SDF_BUCKET_NUM,
-                 n_excess=SDF_EXCESS_LIST_SIZE, device="cuda:0"):
+                 n_excess=SDF_EXCESS_LIST_SIZE, device="cuda:0", use_approximate_raycast=False):
         self.W, self.H = int(width), int(height)
+        # ITMLibSettings::useApproximateRaycast: Prepare forward-projects the last full cast while the camera stays close to it
+        self.use_approximate_raycast = bool(use_approximate_raycast)
+        self._fwd_block = None
+        self._live_colour = None
         self.device = torch.device(device)
         self.voxel_size = float(voxel_size)
         d = self.device
@@ -90,6 +94,8 @@ class TsdfEngine:
         self.frames_processed = 0
         # ITMBasicEngine::camPoses / gtC2wPoses (ITMBasicEngine.h:54-56)
         self.camPoses = []
+        # ITMTrackingState: with given poses too it carries the age and the pose of the point cloud (Prepare runs either way)
+        self.track_state = TrackState()
         self.reset()
 
     def _stream(self):
@@ -99,6 +105,17 @@ class TsdfEngine:
         check(lib.gps_tsdf_reset(C.byref(self.state), self._stream()), "gps_tsdf_reset")
         self.frames_processed = 0
         self.camPoses = []
+        if not hasattr(self, "track_cfg"):   # (a tracker's state is reset by turnOnTracking, as before)
+            check(lib.gps_track_state_reset(C.byref(self.track_state)), "gps_track_state_reset")
+
+    def _forward_block(self):
+        """the forward-render block (gps_tsdf_forward_block_bytes) when the option is on, else NULL: today's path"""
+        if not self.use_approximate_raycast:
+            return None
+        if self._fwd_block is None:
+            nbytes = int(lib.gps_tsdf_forward_block_bytes(self.W, self.H))
+            self._fwd_block = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
+        return self._fwd_block.data_ptr()
 
     # ---- ITMBasicEngine::ProcessFrame (tracking off: pose := gtC2wPoses[framesProcessed]; Coerce())
     def ProcessFrame(self, rgb_u8, depth_mm_i16, gt_c2w):
@@ -111,8 +128,10 @@ class TsdfEngine:
         self._frame_inputs = (rgb_u8, depth_mm_i16)  # keep alive while kernels may read them
         self.state.rgb = rgb_u8.data_ptr()
         M, invM = pose_from_c2w(gt_c2w)
-        check(lib.gps_tsdf_process_frame(C.byref(self.state), depth_mm_i16.data_ptr(), M.ctypes.data,
-                                         invM.ctypes.data, self._stream()), "gps_tsdf_process_frame")
+        # (gps_tsdf_process_frame's launches; Prepare keeps the point cloud's age and pose, and forward-renders if asked to)
+        check(lib.gps_tsdf_process_frame_fwd(C.byref(self.state), depth_mm_i16.data_ptr(), M.ctypes.data, invM.ctypes.data,
+                                             C.byref(self.track_state), self._forward_block(),
+                                             1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_process_frame_fwd")
         self.camPoses.append((M, invM))
         self.frames_processed += 1
         return M, invM
@@ -163,10 +182,17 @@ class TsdfEngine:
         assert rgb_u8.is_contiguous() and depth_mm_i16.is_contiguous()
         self._frame_inputs = (rgb_u8, depth_mm_i16)
         self.state.rgb = rgb_u8.data_ptr()
-        check(lib.gps_tsdf_process_frame_tracked(C.byref(self.state), depth_mm_i16.data_ptr(), C.byref(self.track_cfg),
-                                                 C.byref(self.track_state), self.track_scratch.data_ptr(),
-                                                 self.track_scratch.numel(), self._stream()),
-              "gps_tsdf_process_frame_tracked")
+        if self.use_approximate_raycast:   # the two halves of gps_tsdf_process_frame_tracked, Prepare with the forward render
+            check(lib.gps_tsdf_frame_track(C.byref(self.state), depth_mm_i16.data_ptr(), C.byref(self.track_cfg),
+                                           C.byref(self.track_state), self.track_scratch.data_ptr(), self.track_scratch.numel(),
+                                           self._stream()), "gps_tsdf_frame_track")
+            check(lib.gps_tsdf_frame_map_fwd(C.byref(self.state), C.byref(self.track_state), 1, 0, self._forward_block(), 1,
+                                             self._stream()), "gps_tsdf_frame_map_fwd")
+        else:
+            check(lib.gps_tsdf_process_frame_tracked(C.byref(self.state), depth_mm_i16.data_ptr(), C.byref(self.track_cfg),
+                                                     C.byref(self.track_state), self.track_scratch.data_ptr(),
+                                                     self.track_scratch.numel(), self._stream()),
+                  "gps_tsdf_process_frame_tracked")
         M = np.array(self.track_state.pose_M, dtype=np.float32)
         invM = np.array(self.track_state.pose_invM, dtype=np.float32)
         self.camPoses.append((M, invM))
@@ -192,6 +218,15 @@ class TsdfEngine:
 
     # ---- ITMBasicEngine::runRaycast(pose, intrinsics) + GetFreeImage / GetFreeVertex
     def runRaycast(self, c2w=None, pose=None):
+        if c2w is None and pose is None:
+            # runRaycast(NULL, NULL) (ITMBasicEngine.tpp:503-518): the live view in colour, from the last full cast while it is
+            # current (age <= 0), from the forward projection afterwards -> GetLiveImage()
+            if self._live_colour is None:
+                self._live_colour = torch.zeros(self.W * self.H * 4, dtype=torch.uint8, device=self.device)
+            check(lib.gps_tsdf_render_live(C.byref(self.state), C.byref(self.track_state),
+                                           self._fwd_block.data_ptr() if self._fwd_block is not None else None,
+                                           self._live_colour.data_ptr(), self._stream()), "gps_tsdf_render_live")
+            return None
         M, invM = pose if pose is not None else pose_from_c2w(c2w)
         check(lib.gps_tsdf_free_raycast(C.byref(self.state), M.ctypes.data, invM.ctypes.data, self._stream()),
               "gps_tsdf_free_raycast")
@@ -242,6 +277,28 @@ class TsdfEngine:
 
     def GetLiveVertex(self):
         return self.raycast.view(self.H, self.W, 4)
+
+    def GetLiveImage(self):
+        """uchar4 [H,W,4] of the last runRaycast() without a pose"""
+        return self._live_colour.view(self.H, self.W, 4)
+
+    def GetForwardProjection(self):
+        """renderState->forwardProjection: float4 [H,W,4] of the last forward render (None before the option's first frame)"""
+        if self._fwd_block is None:
+            return None
+        return self._fwd_block[:self.W * self.H * 4].view(torch.float32).view(self.H, self.W, 4)
+
+    def forwardMissingPoints(self):
+        """(noFwdProjMissingPoints, the missing list sorted) of the last forward render; blocking read-back: tests / statistics"""
+        n = C.c_int32(0)
+        lst = np.zeros(self.W * self.H, np.int32)
+        check(lib.gps_tsdf_forward_missing(C.byref(self.state), self._fwd_block.data_ptr(), C.byref(n), lst.ctypes.data, lst.size,
+                                           self._stream()), "gps_tsdf_forward_missing")
+        return int(n.value), np.sort(lst[:n.value])
+
+    @property
+    def age_pointCloud(self):
+        return int(self.track_state.age_point_cloud)
 
     def getVoxelSize(self):
         return self.voxel_size

@@ -1071,6 +1071,51 @@ GPS_API int gps_tsdf_frame_track(const gps_tsdf_state *s, const int16_t *depth_m
                                  void *scratch, int64_t scratch_bytes, gps_stream stream);
 GPS_API int gps_tsdf_frame_map(const gps_tsdf_state *s, gps_track_state *ts, int fuse, int reset_visible, gps_stream stream);
 
+/* ---- approximate raycast by forward projection (ITMLibSettings::useApproximateRaycast; csrc/tsdf_forward.hip) -------------
+ * While the camera stays close to the pose of the last full cast, ITMTrackingController::Prepare does not cast the image again:
+ * it keeps the ICP maps (the tracker goes on aligning against them with scenePose = pose_pointCloud), projects the last full
+ * cast (s->raycast, never a previous forward projection) into the new pose and casts rays only for the pixels the projection
+ * left empty (ForwardRender).  Off unless asked for; everything is stream-ordered, the missing count stays on the device.
+ *
+ * The forward-render block is caller-allocated device memory of gps_tsdf_forward_block_bytes(width, height) bytes, 16-byte
+ * aligned, owned by the library between calls.  With P = width * height: float4[P] forward projection at offset 0 (voxel units,
+ * w as s->raycast), int32[P] winner image at 16 P (source index whose ray landed on the pixel, -1: none), int32[P] missing list
+ * at 20 P (pixel indices, order unspecified), int32[16] at 24 P ([0] = length of the list). */
+GPS_API int64_t gps_tsdf_forward_block_bytes(int width, int height);
+/* ForwardRender_common at pose M / invM over s->raycast, s->minmax (CreateExpectedDepths at the same pose comes first) and
+ * s->depth.  _project: forward projection (highest source index wins a target, as the CPU engine's scan order has it) and the
+ * missing list; _fill: castRay without visible-list writes for the listed pixels, bit-equal to what gps_tsdf_raycast(...,
+ * update_visible = 0) writes for them; _render: both. */
+GPS_API int gps_tsdf_forward_project(const gps_tsdf_state *s, void *block, const float *M, gps_stream stream);
+GPS_API int gps_tsdf_forward_fill(const gps_tsdf_state *s, void *block, const float *invM, gps_stream stream);
+GPS_API int gps_tsdf_forward_render(const gps_tsdf_state *s, void *block, const float *M, const float *invM, gps_stream stream);
+/* Tests / statistics (blocking read-back, never called in the frame chain): noFwdProjMissingPoints of the last forward render
+ * on this block -> *count_out, and its first min(count, capacity) list entries -> list_out (may be NULL with capacity 0). */
+GPS_API int gps_tsdf_forward_missing(const gps_tsdf_state *s, const void *block, int32_t *count_out, int32_t *list_out, int capacity,
+                                     gps_stream stream);
+/* ITMTrackingState::TrackerFarFromPointCloud (host only): 1 if there is no point cloud yet (age < 0), it is older than 5 frames,
+ * or the camera centre moved more than sqrt(0.0005) m from pose_pointCloud; else 0.  *diff_out (optional): the squared distance. */
+GPS_API int gps_track_far_from_point_cloud(const gps_track_state *ts, float *diff_out);
+/* ITMTrackingController::Prepare at ts->pose_M / pose_invM (depth tracker): expected depths, then either the full cast + ICP maps
+ * with pose_pointCloud := pose_d and age := 0 (-2 on the first frame), or -- use_approximate_raycast != 0, a block given and the
+ * tracker not far from the point cloud -- the forward render with age + 1.  fwd_block NULL or use_approximate_raycast 0: exactly
+ * the launches of gps_tsdf_expected_depths_and_raycast + gps_tsdf_icp_maps. */
+GPS_API int gps_tsdf_prepare(const gps_tsdf_state *s, gps_track_state *ts, void *fwd_block, int use_approximate_raycast,
+                             gps_stream stream);
+/* gps_tsdf_frame_map with that Prepare (gps_tsdf_frame_map is this with a NULL block). */
+GPS_API int gps_tsdf_frame_map_fwd(const gps_tsdf_state *s, gps_track_state *ts, int fuse, int reset_visible, void *fwd_block,
+                                   int use_approximate_raycast, gps_stream stream);
+/* gps_tsdf_process_frame (given pose) with that Prepare: ts->pose := M / invM, convert, allocate, integrate, Prepare -- the
+ * tracking state keeps the age and the pose of the point cloud with tracking switched off as well (ITMBasicEngine.tpp:355). */
+GPS_API int gps_tsdf_process_frame_fwd(const gps_tsdf_state *s, const int16_t *depth_mm, const float *M, const float *invM,
+                                       gps_track_state *ts, void *fwd_block, int use_approximate_raycast, gps_stream stream);
+/* drawPixelColour over any ray image of the state's size (float4 [H*W], voxel units) -> uchar4 [H*W]. */
+GPS_API int gps_tsdf_render_colour_from(const gps_tsdf_state *s, const float *rays, uint8_t *colour_out, gps_stream stream);
+/* ITMBasicEngine::runRaycast(NULL, NULL): the live view in colour from the volume, rendered from s->raycast while
+ * ts->age_point_cloud <= 0 and from the block's forward projection afterwards (fwd_block may be NULL in the first case). */
+GPS_API int gps_tsdf_render_live(const gps_tsdf_state *s, const gps_track_state *ts, const void *fwd_block, uint8_t *colour_out,
+                                 gps_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
