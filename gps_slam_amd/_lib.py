@@ -156,6 +156,10 @@ PROTOTYPES = {
     "gps_tsdf_process_frame_fwd": (i32, [C.POINTER(TsdfState), vp, vp, vp, C.POINTER(TrackState), vp, i32, vp]),
     "gps_tsdf_render_colour_from": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_render_live": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), vp, vp, vp]),
+    "gps_tsdf_render_image": (i32, [C.POINTER(TsdfState), vp, i32, i32, vp, i32, vp, vp]),
+    "gps_tsdf_depth_to_rgba8_scratch_bytes": (i64, []),
+    "gps_tsdf_depth_to_rgba8": (i32, [vp, i32, vp, vp, vp]),
+    "gps_tsdf_get_image": (i32, [C.POINTER(TsdfState), vp, vp, i32, vp, vp]),
     "gps_tsdf_convert_depth": (i32, [C.POINTER(TsdfState), vp, vp]),
     "gps_tsdf_allocate": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_integrate": (i32, [C.POINTER(TsdfState), vp, vp]),

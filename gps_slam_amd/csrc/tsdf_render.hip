@@ -16,6 +16,7 @@
 
 #include "launch_timing.hpp"
 #include "tsdf_common.hpp"
+#include "tsdf_normals.hpp"
 #include "tsdf_pose.hpp"
 #include "tsdf_voxel.hpp"
 #include "wave_reduce.hpp"
@@ -437,36 +438,8 @@ __global__ __launch_bounds__(256) void icp_kernel(TsdfState s, Mat4 invM, const 
     const int loc = x + y * W;
     const float4 point = pr[loc];
     bool found = point.w > 0.0f;
-    float nx = 0.f, ny = 0.f, nz = 0.f;
-    if (found && (y <= 2 || y >= H - 3 || x <= 2 || x >= W - 3)) found = false;
-    if (found) {
-        float4 xp = pr[(x + 2) + y * W], yp = pr[x + (y + 2) * W], xm = pr[(x - 2) + y * W], ym = pr[x + (y - 2) * W];
-        float dxx = 0.f, dxy = 0.f, dxz = 0.f, dyx = 0.f, dyy = 0.f, dyz = 0.f;
-        bool doPlus1 = false;
-        if (xp.w <= 0 || yp.w <= 0 || xm.w <= 0 || ym.w <= 0) doPlus1 = true;
-        else {
-            dxx = xp.x - xm.x; dxy = xp.y - xm.y; dxz = xp.z - xm.z;
-            dyx = yp.x - ym.x; dyy = yp.y - ym.y; dyz = yp.z - ym.z;
-            const float la = dxx * dxx + dxy * dxy + dxz * dxz, lb = dyx * dyx + dyy * dyy + dyz * dyz;
-            const float ld = (la < lb) ? lb : la;
-            if (ld * s.voxel_size * s.voxel_size > (0.15f * 0.15f)) doPlus1 = true;
-        }
-        if (doPlus1) {
-            xp = pr[(x + 1) + y * W]; yp = pr[x + (y + 1) * W]; xm = pr[(x - 1) + y * W]; ym = pr[x + (y - 1) * W];
-            dxx = xp.x - xm.x; dxy = xp.y - xm.y; dxz = xp.z - xm.z;
-            dyx = yp.x - ym.x; dyy = yp.y - ym.y; dyz = yp.z - ym.z;
-            if (xp.w <= 0 || yp.w <= 0 || xm.w <= 0 || ym.w <= 0) found = false;
-        }
-        if (found) {
-            nx = -(dxy * dyz - dxz * dyy);
-            ny = -(dxz * dyx - dxx * dyz);
-            nz = -(dxx * dyy - dxy * dyx);
-            const float ns = 1.0f / sqrtf(nx * nx + ny * ny + nz * nz);
-            nx *= ns; ny *= ns; nz *= ns;
-            const float angle = nx * (-invM.m[8]) + ny * (-invM.m[9]) + nz * (-invM.m[10]);
-            if (!(angle > 0.0)) found = false;
-        }
-    }
+    float nx = 0.f, ny = 0.f, nz = 0.f, angle;
+    if (found) found = image_normal_and_angle(pr, x, y, W, H, s.voxel_size, invM, nx, ny, nz, angle);   // (tsdf_normals.hpp)
     if (found) {
         points[loc] = make_float4(point.x * s.voxel_size, point.y * s.voxel_size, point.z * s.voxel_size, point.w);
         normals[loc] = make_float4(nx, ny, nz, 0.0f);
@@ -512,7 +485,8 @@ __global__ __launch_bounds__(256) void raycast_maps_kernel(int P, const float4* 
 // readFromSDF_color4u_interpolated, GPS-SLAM variant renormalised over w_color >= 1
 // (ITMRepresentationAccess.h:344-423) + drawPixelColour (Shared.h:384-394)
 __global__ __launch_bounds__(256) void colour_kernel(TsdfState s, const float4* __restrict__ rays, uchar4* __restrict__ out,
-                                                    const ViewRec* __restrict__ views) {
+                                                    const ViewRec* __restrict__ views, gps::LaunchStamp stamp) {
+    gps::StampScope timed(stamp);
     GPS_FRAME_PRIO();
     const ViewRec* maps = nullptr;  // the view's tensor glue rides on this kernel (it holds the ray and the colour of the pixel)
     if (views) {
@@ -639,7 +613,7 @@ int gps_tsdf_free_raycast_batch(const gps_tsdf_state* sp, int n_views, const gps
     // (pass B of the expected depths rides in the raycaster)
     raycast_kernel<false><<<grid, 256, 0, st>>>(s, none, nullptr, nullptr, bucket_bits(s), tab, nullptr, sw, sh, nullptr, gps::LaunchStamp{nullptr});
 #endif
-    colour_kernel<<<dim3(gps_div_up(s.width, 16), gps_div_up(s.height, 16), n_views), 256, 0, st>>>(s, nullptr, nullptr, tab);
+    colour_kernel<<<dim3(gps_div_up(s.width, 16), gps_div_up(s.height, 16), n_views), 256, 0, st>>>(s, nullptr, nullptr, tab, gps::LaunchStamp{nullptr});
     GPS_LAUNCH_CHECK();
     return GPS_OK;
 }
@@ -771,8 +745,9 @@ int gps_tsdf_render_colour(const gps_tsdf_state* sp, gps_stream stream) {
     GPS_REQUIRE(state_valid(*sp));
     TsdfState s = *sp;
     dim3 grid(gps_div_up(s.width, 16), gps_div_up(s.height, 16));
-    colour_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(s, reinterpret_cast<const float4*>(s.fv_raycast),
-                                                        reinterpret_cast<uchar4*>(s.fv_colour), nullptr);
+    const ViewRec* no_table = nullptr;
+    gps::launch_kernel(gps::TK_RENDER_COLOUR, 0, colour_kernel, grid, dim3(256), 0, (hipStream_t)stream, s, reinterpret_cast<const float4*>(s.fv_raycast),
+                       reinterpret_cast<uchar4*>(s.fv_colour), no_table);
     GPS_LAUNCH_CHECK();
     return GPS_OK;
 }
@@ -783,8 +758,9 @@ int gps_tsdf_render_colour_from(const gps_tsdf_state* sp, const float* rays, uin
     GPS_REQUIRE(state_valid(*sp));
     TsdfState s = *sp;
     dim3 grid(gps_div_up(s.width, 16), gps_div_up(s.height, 16));
-    colour_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(s, reinterpret_cast<const float4*>(rays), reinterpret_cast<uchar4*>(colour_out),
-                                                        nullptr);
+    const ViewRec* no_table = nullptr;
+    gps::launch_kernel(gps::TK_RENDER_COLOUR, 0, colour_kernel, grid, dim3(256), 0, (hipStream_t)stream, s, reinterpret_cast<const float4*>(rays),
+                       reinterpret_cast<uchar4*>(colour_out), no_table);
     GPS_LAUNCH_CHECK();
     return GPS_OK;
 }

@@ -303,6 +303,39 @@ PYBIND11_MODULE(_host, m) {
         .value("TRACKING_POOR", ITMTrackingState::TRACKING_POOR)
         .value("TRACKING_FAILED", ITMTrackingState::TRACKING_FAILED);
     m.def("failureModeFromString", &ITMLib::ITMLibSettings::failureModeFromString);
+    // ---- ITMMainEngine::GetImageType and what GetImage does with it (tsdf_engine.hpp, decideOnGetImage)
+    {
+        typedef ITMLib::ITMMainEngineTypes T;
+        py::enum_<T::GetImageType>(m, "GetImageType")
+            .value("InfiniTAM_IMAGE_ORIGINAL_RGB", T::InfiniTAM_IMAGE_ORIGINAL_RGB)
+            .value("InfiniTAM_IMAGE_ORIGINAL_DEPTH", T::InfiniTAM_IMAGE_ORIGINAL_DEPTH)
+            .value("InfiniTAM_IMAGE_SCENERAYCAST", T::InfiniTAM_IMAGE_SCENERAYCAST)
+            .value("InfiniTAM_IMAGE_COLOUR_FROM_VOLUME", T::InfiniTAM_IMAGE_COLOUR_FROM_VOLUME)
+            .value("InfiniTAM_IMAGE_COLOUR_FROM_NORMAL", T::InfiniTAM_IMAGE_COLOUR_FROM_NORMAL)
+            .value("InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE", T::InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE)
+            .value("InfiniTAM_IMAGE_FREECAMERA_SHADED", T::InfiniTAM_IMAGE_FREECAMERA_SHADED)
+            .value("InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME", T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME)
+            .value("InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL", T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL)
+            .value("InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE", T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE)
+            .value("InfiniTAM_IMAGE_UNKNOWN", T::InfiniTAM_IMAGE_UNKNOWN);
+        py::enum_<ITMLib::GetImageDecision::RaySource>(m, "GetImageRaySource")
+            .value("RAYS_NONE", ITMLib::GetImageDecision::RAYS_NONE)
+            .value("RAYS_LIVE_RAYCAST", ITMLib::GetImageDecision::RAYS_LIVE_RAYCAST)
+            .value("RAYS_FORWARD_PROJECTION", ITMLib::GetImageDecision::RAYS_FORWARD_PROJECTION)
+            .value("RAYS_FREE_RAYCAST", ITMLib::GetImageDecision::RAYS_FREE_RAYCAST);
+        py::enum_<ITMLib::GetImageDecision::OutSource>(m, "GetImageOutSource")
+            .value("OUT_CLEARED", ITMLib::GetImageDecision::OUT_CLEARED)
+            .value("OUT_RGB", ITMLib::GetImageDecision::OUT_RGB)
+            .value("OUT_DEPTH_COLOUR", ITMLib::GetImageDecision::OUT_DEPTH_COLOUR)
+            .value("OUT_LIVE_RENDER", ITMLib::GetImageDecision::OUT_LIVE_RENDER)
+            .value("OUT_KF_RAYCAST", ITMLib::GetImageDecision::OUT_KF_RAYCAST)
+            .value("OUT_FREE_RENDER", ITMLib::GetImageDecision::OUT_FREE_RENDER);
+        py::class_<ITMLib::GetImageDecision>(m, "GetImageDecision")
+            .def_readonly("renderType", &ITMLib::GetImageDecision::renderType)
+            .def_readonly("rays", &ITMLib::GetImageDecision::rays)
+            .def_readonly("out", &ITMLib::GetImageDecision::out);
+        m.def("decideOnGetImage", &ITMLib::decideOnGetImage, py::arg("type"), py::arg("age_pointCloud"), py::arg("relocalisationCount"));
+    }
     py::class_<ITMLib::FailureDecision>(m, "FailureDecision")
         .def_readonly("result", &ITMLib::FailureDecision::result)
         .def_readonly("useRelocaliser", &ITMLib::FailureDecision::useRelocaliser)
@@ -481,6 +514,41 @@ PYBIND11_MODULE(_host, m) {
         .def("GetLiveImage", &TsdfEngine::GetLiveImage)
         .def("GetForwardProjection", &TsdfEngine::GetForwardProjection)
         .def("forwardMissingPoints", &TsdfEngine::forwardMissingPoints)
+        // ---- ITMBasicEngine::GetImage: the type by name ("InfiniTAM_IMAGE_SCENERAYCAST" or "SCENERAYCAST"), enumerator or value;
+        // c2w (and optionally fx, fy, cx, cy) for the free-camera types.  -> uint8 [H, W, 4] device tensor, None before the first frame
+        .def("GetImage", [](TsdfEngine& e, const py::object& type, const c10::optional<torch::Tensor>& c2w,
+                            const c10::optional<std::vector<float>>& intrinsics, bool to_host) -> py::object {
+            typedef ITMLib::ITMMainEngineTypes T;
+            T::GetImageType t;
+            if (py::isinstance<py::str>(type)) {
+                std::string name = type.cast<std::string>();
+                if (name.rfind("InfiniTAM_IMAGE_", 0) != 0) name = "InfiniTAM_IMAGE_" + name;
+                const py::dict members = py::cast(T::InfiniTAM_IMAGE_UNKNOWN).get_type().attr("__members__");
+                TORCH_CHECK(members.contains(name.c_str()), "GetImage: unknown image type '", name, "'");
+                t = members[name.c_str()].cast<T::GetImageType>();
+            } else if (py::isinstance<T::GetImageType>(type)) {
+                t = type.cast<T::GetImageType>();
+            } else {
+                const int v = type.cast<int>();
+                TORCH_CHECK(v >= 0 && v <= (int)T::InfiniTAM_IMAGE_UNKNOWN, "GetImage: image type ", v, " out of range");
+                t = (T::GetImageType)v;
+            }
+            ORUtils::SE3Pose pose;
+            ITMLib::ITMIntrinsics in;
+            if (c2w) { auto c = c2w->to(torch::kCPU, torch::kFloat32).contiguous(); pose.SetInvM(c.data_ptr<float>()); }
+            if (intrinsics) {
+                TORCH_CHECK(intrinsics->size() == 4, "GetImage: intrinsics are (fx, fy, cx, cy)");
+                in.SetFrom(e.state().width, e.state().height, (*intrinsics)[0], (*intrinsics)[1], (*intrinsics)[2], (*intrinsics)[3]);
+            }
+            if (to_host) {   // the reference's signature: into a caller's host image (synchronous)
+                ITMUChar4Image img(Vector2i(e.state().width, e.state().height), true, false);
+                std::memset(img.GetData(MEMORYDEVICE_CPU), 0xAB, img.dataSize() * 4);   // (shows an image left untouched)
+                e.GetImage(&img, t, c2w ? &pose : nullptr, intrinsics ? &in : nullptr);
+                return py::cast(img.host_tensor().clone().view({e.state().height, e.state().width, 4}));
+            }
+            torch::Tensor r = e.getImageTensor(t, c2w ? &pose : nullptr, intrinsics ? &in : nullptr);
+            return r.defined() ? py::cast(r) : py::none();
+        }, py::arg("image_type"), py::arg("c2w") = py::none(), py::arg("intrinsics") = py::none(), py::arg("to_host") = false)
         .def("getVoxelSize", &TsdfEngine::getVoxelSize)
         .def("counters", &TsdfEngine::counters)
         .def("MeshScene", &TsdfEngine::MeshScene, py::arg("maxTriangles") = (int64_t)1 << 24)

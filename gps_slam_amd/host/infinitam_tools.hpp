@@ -22,9 +22,11 @@
 namespace ITMLib {
 
 // ITMLib/Core/ITMMainEngine.h:39-88 (the members GPS-SLAM calls)
-class ITMMainEngine {
+class ITMMainEngine : public ITMMainEngineTypes {   // (GetImageType, InfiniTAM_IMAGE_*: tsdf_engine.hpp)
 public:
     virtual ~ITMMainEngine() {}
+    virtual void GetImage(ITMUChar4Image* out, GetImageType getImageType, ORUtils::SE3Pose* pose = NULL,
+                          ITMIntrinsics* intrinsics = NULL) = 0;
     virtual ITMTrackingState* GetTrackingState(void) = 0;
     virtual ITMTrackingState::TrackingResult ProcessFrame(ITMUChar4Image* rgbImage, ITMShortImage* rawDepthImage,
                                                           ITMIMUMeasurement* imuMeasurement = NULL) = 0;
@@ -69,6 +71,10 @@ public:
     void SaveToFile(const std::string& d) override { TsdfEngine::SaveToFile(d); }
     void LoadFromFile(const std::string& d) override { TsdfEngine::LoadFromFile(d); }
     Vector2i GetImageSize(void) const override { return Vector2i(state().width, state().height); }
+    void GetImage(ITMUChar4Image* out, ITMMainEngine::GetImageType getImageType, ORUtils::SE3Pose* pose = NULL,
+                  ITMIntrinsics* intrinsics = NULL) override {
+        TsdfEngine::GetImage(out, getImageType, pose, intrinsics);
+    }
     void turnOnTracking() override { TsdfEngine::turnOnTracking(); }
     void turnOffTracking() override { TsdfEngine::turnOffTracking(); }
 };

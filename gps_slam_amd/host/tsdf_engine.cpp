@@ -301,6 +301,85 @@ void TsdfEngine::runRaycast(ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intri
     check(gps_tsdf_free_raycast(&s, pose->GetM(), pose->GetInvM(), current_stream()), "gps_tsdf_free_raycast");
 }
 
+// ITMBasicEngine::GetImage (ITMBasicEngine.tpp:394-498): renders what the type asks for and returns the engine's image the
+// caller's copy comes from (an undefined tensor: the cleared image)
+torch::Tensor TsdfEngine::getImageSource(GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics) {
+    using D = ITMLib::GetImageDecision;
+    const D d = ITMLib::decideOnGetImage(type, track_state_.age_point_cloud, relocalisationCount);
+    const gps_stream st = current_stream();
+    const int W = state_.width, H = state_.height;
+    const int64_t P = (int64_t)W * H;
+    auto image = [&](torch::Tensor& t) -> torch::Tensor& {
+        if (!t.defined()) t = zeros_bytes(P * 4, device_).view({H, W, 4});
+        return t;
+    };
+    switch (d.out) {
+    case D::OUT_RGB: return currentRgb();
+    case D::OUT_DEPTH_COLOUR:
+        if (!depth_colour_scratch_.defined()) depth_colour_scratch_ = zeros_bytes(gps_tsdf_depth_to_rgba8_scratch_bytes(), device_);
+        check(gps_tsdf_depth_to_rgba8(state_.depth, (int)P, depth_colour_scratch_.data_ptr(), ptr<uint8_t>(image(depth_colour_)), st),
+              "gps_tsdf_depth_to_rgba8");
+        return depth_colour_;
+    case D::OUT_LIVE_RENDER:
+    case D::OUT_KF_RAYCAST: {
+        const float* rays = state_.raycast;
+        if (d.rays == D::RAYS_FORWARD_PROJECTION) {
+            TORCH_CHECK(fwd_block_.defined(), "GetImage: the point cloud has an age but there is no forward projection");
+            rays = static_cast<const float*>(fwd_block_.data_ptr());
+        }
+        // (the intrinsics the live types render with are the depth camera's: state_.fx / fy decide the flipNormals refusal)
+        check(gps_tsdf_render_image(&state_, rays, W, H, pose_d_.GetInvM(), d.renderType, ptr<uint8_t>(image(live_colour_)), st),
+              "gps_tsdf_render_image");
+        // kfRaycast is never written after its construction in this reference (addKeyframeIdx is never assigned,
+        // ITMBasicEngine.tpp:303, 357): a cleared image, and no copy into it here either
+        return d.out == D::OUT_KF_RAYCAST ? image(kf_raycast_) : live_colour_;
+    }
+    case D::OUT_FREE_RENDER: {
+        TORCH_CHECK(pose != nullptr, "GetImage: a free-camera image needs a pose");
+        gps_tsdf_state s;
+        { std::lock_guard<std::mutex> lk(state_mu_); s = state_; }
+        if (intrinsics) {
+            TORCH_CHECK(intrinsics->imgSize.x == s.width && intrinsics->imgSize.y == s.height,
+                        "GetImage: the free-view render state has the depth camera's image size");
+            s.fx = intrinsics->projectionParamsSimple.fx; s.fy = intrinsics->projectionParamsSimple.fy;
+            s.cx = intrinsics->projectionParamsSimple.px; s.cy = intrinsics->projectionParamsSimple.py;
+        }
+        check(gps_tsdf_get_image(&s, pose->GetM(), pose->GetInvM(), d.renderType, nullptr, st), "gps_tsdf_get_image");
+        return fv_colour_.view({H, W, 4});
+    }
+    default: return torch::Tensor();
+    }
+}
+
+torch::Tensor TsdfEngine::getImageTensor(GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics) {
+    if (framesSeen == 0) return torch::Tensor();   // (view == NULL)
+    const torch::Tensor src = getImageSource(type, pose, intrinsics);
+    if (!src.defined()) return zeros_bytes((int64_t)state_.width * state_.height * 4, device_).view({state_.height, state_.width, 4});
+    return src.view({state_.height, state_.width, 4}).clone();
+}
+
+void TsdfEngine::GetImage(ITMUChar4Image* out, GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics) {
+    if (framesSeen == 0) return;   // (view == NULL)
+    TORCH_CHECK(out != nullptr, "GetImage: null image");
+    TORCH_CHECK(out->noDims.x == state_.width && out->noDims.y == state_.height, "GetImage: the image must have the engine's size");
+    const torch::Tensor src = getImageSource(type, pose, intrinsics);
+    const size_t bytes = (size_t)state_.width * state_.height * 4;
+    hipStream_t st = (hipStream_t)current_stream();
+    if (out->isAllocated_CUDA()) {
+        TORCH_CHECK((src.defined() ? hipMemcpyAsync(out->GetData(MEMORYDEVICE_CUDA), src.data_ptr(), bytes, hipMemcpyDeviceToDevice, st)
+                                   : hipMemsetAsync(out->GetData(MEMORYDEVICE_CUDA), 0, bytes, st)) == hipSuccess, "GetImage: device copy failed");
+    }
+    if (out->isAllocated_CPU()) {
+        if (src.defined()) {
+            TORCH_CHECK(hipMemcpyAsync(out->GetData(MEMORYDEVICE_CPU), src.data_ptr(), bytes, hipMemcpyDeviceToHost, st) == hipSuccess,
+                        "GetImage: download failed");
+            TORCH_CHECK(hipStreamSynchronize(st) == hipSuccess, "GetImage: hipStreamSynchronize");
+        } else {
+            std::memset(out->GetData(MEMORYDEVICE_CPU), 0, bytes);
+        }
+    }
+}
+
 void* TsdfEngine::forwardBlock() {
     if (!useApproximateRaycast) return nullptr;
     if (!fwd_block_.defined()) fwd_block_ = zeros_bytes(gps_tsdf_forward_block_bytes(state_.width, state_.height), device_);

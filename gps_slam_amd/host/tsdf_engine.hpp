@@ -188,6 +188,72 @@ inline FailureDecision decideOnTrackingResult(ITMLibSettings::FailureMode mode, 
     return d;
 }
 
+// ITMLib/Core/ITMMainEngine.h:50-63: the images GetImage can be asked for (ITMMainEngine derives from this, so that
+// ITMMainEngine::GetImageType and ITMMainEngine::InfiniTAM_IMAGE_* read as in the reference)
+struct ITMMainEngineTypes {
+    enum GetImageType {
+        InfiniTAM_IMAGE_ORIGINAL_RGB,
+        InfiniTAM_IMAGE_ORIGINAL_DEPTH,
+        InfiniTAM_IMAGE_SCENERAYCAST,
+        InfiniTAM_IMAGE_COLOUR_FROM_VOLUME,
+        InfiniTAM_IMAGE_COLOUR_FROM_NORMAL,
+        InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE,
+        InfiniTAM_IMAGE_FREECAMERA_SHADED,
+        InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME,
+        InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL,
+        InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE,
+        InfiniTAM_IMAGE_UNKNOWN
+    };
+};
+
+// What ITMBasicEngine::GetImage does for an image type (ITMBasicEngine.tpp:400-497), as one pure function of the type, the age of
+// the point cloud and the relocalisation countdown.
+//   renderType   the RenderImage pass (gps_render_type), -1: none
+//   rays         the ray image that pass reads: the last full cast (age_pointCloud <= 0), the forward projection (otherwise), or a
+//                fresh cast of the free view that leaves the visible list alone
+//   out          where the caller's image comes from.  OUT_KF_RAYCAST: the live types while relocalisationCount != 0 -- the live
+//                image is rendered all the same, and the caller gets kfRaycast, which this reference never writes (all zeros).
+//                OUT_CLEARED: InfiniTAM_IMAGE_UNKNOWN, the cleared image
+struct GetImageDecision {
+    enum RaySource { RAYS_NONE, RAYS_LIVE_RAYCAST, RAYS_FORWARD_PROJECTION, RAYS_FREE_RAYCAST };
+    enum OutSource { OUT_CLEARED, OUT_RGB, OUT_DEPTH_COLOUR, OUT_LIVE_RENDER, OUT_KF_RAYCAST, OUT_FREE_RENDER };
+    int renderType;
+    RaySource rays;
+    OutSource out;
+};
+inline GetImageDecision decideOnGetImage(ITMMainEngineTypes::GetImageType type, int age_pointCloud, int relocalisationCount) {
+    typedef ITMMainEngineTypes T;
+    GetImageDecision d{-1, GetImageDecision::RAYS_NONE, GetImageDecision::OUT_CLEARED};
+    switch (type) {
+    case T::InfiniTAM_IMAGE_ORIGINAL_RGB: d.out = GetImageDecision::OUT_RGB; break;
+    case T::InfiniTAM_IMAGE_ORIGINAL_DEPTH: d.out = GetImageDecision::OUT_DEPTH_COLOUR; break;
+    case T::InfiniTAM_IMAGE_SCENERAYCAST:
+    case T::InfiniTAM_IMAGE_COLOUR_FROM_VOLUME:
+    case T::InfiniTAM_IMAGE_COLOUR_FROM_NORMAL:
+    case T::InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE:
+        d.rays = age_pointCloud <= 0 ? GetImageDecision::RAYS_LIVE_RAYCAST : GetImageDecision::RAYS_FORWARD_PROJECTION;
+        d.renderType = type == T::InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE ? GPS_RENDER_COLOUR_FROM_CONFIDENCE
+                       : type == T::InfiniTAM_IMAGE_COLOUR_FROM_NORMAL   ? GPS_RENDER_COLOUR_FROM_NORMAL
+                       : type == T::InfiniTAM_IMAGE_COLOUR_FROM_VOLUME   ? GPS_RENDER_COLOUR_FROM_VOLUME
+                                                                         : GPS_RENDER_SHADED_GREYSCALE_IMAGENORMALS;
+        d.out = relocalisationCount != 0 ? GetImageDecision::OUT_KF_RAYCAST : GetImageDecision::OUT_LIVE_RENDER;
+        break;
+    case T::InfiniTAM_IMAGE_FREECAMERA_SHADED:
+    case T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME:
+    case T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL:
+    case T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE:
+        d.rays = GetImageDecision::RAYS_FREE_RAYCAST;
+        d.renderType = type == T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME       ? GPS_RENDER_COLOUR_FROM_VOLUME
+                       : type == T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL     ? GPS_RENDER_COLOUR_FROM_NORMAL
+                       : type == T::InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE ? GPS_RENDER_COLOUR_FROM_CONFIDENCE
+                                                                                      : GPS_RENDER_SHADED_GREYSCALE;
+        d.out = GetImageDecision::OUT_FREE_RENDER;
+        break;
+    default: break;
+    }
+    return d;
+}
+
 // The verdict itself.  The reference's comes from an SVM over four tracker statistics whose weights are constants of its source
 // (ITMExtendedTracker::UpdatePoseQuality); they are not shipped here.  In their place: thresholds on the residual score the tracker
 // already reports -- two of the SVM's four inputs: the residual score (trackDiag(10): the root of the mean robust residual, the
@@ -262,6 +328,19 @@ public:
     torch::Tensor GetLiveImage() const { return live_colour_; }   // uchar4 [H,W,4] of the last runRaycast(NULL, NULL)
     // (noFwdProjMissingPoints, the list) of the last forward render: blocking read-back, tests / statistics only
     std::pair<int, torch::Tensor> forwardMissingPoints() const;
+    // ---- ITMBasicEngine::GetImage (ITMBasicEngine.tpp:394-498; decideOnGetImage above).  Before the first frame (view == NULL)
+    // `out` is left untouched.  The live types render the last full cast while it is current and the forward projection afterwards
+    // into the live render image (GetLiveImage()); SCENERAYCAST shades from the ray image's own normals, the others from the
+    // volume.  While relocalisationCount != 0 they answer kfRaycast -- which the reference never writes (addKeyframeIdx is never
+    // assigned): a cleared image.  The free-camera types run FindVisibleBlocks + CreateExpectedDepths + a cast that leaves the
+    // visible list alone into the free-view render state (GetFreeImage()) at `pose` / `intrinsics` (NULL: the depth camera's;
+    // the image size is the depth image's).  out must have the engine's image size; a host copy is filled and the stream
+    // synchronised (the reference's GetImage is synchronous), a device copy is filled in stream order.
+    typedef ITMLib::ITMMainEngineTypes::GetImageType GetImageType;
+    void GetImage(ITMUChar4Image* out, GetImageType getImageType, ORUtils::SE3Pose* pose = NULL, ITMLib::ITMIntrinsics* intrinsics = NULL);
+    // the same on the device: uint8 [H, W, 4], a tensor of its own, written on the current stream; no synchronisation.
+    // Undefined before the first frame.
+    torch::Tensor getImageTensor(GetImageType getImageType, ORUtils::SE3Pose* pose = NULL, ITMLib::ITMIntrinsics* intrinsics = NULL);
     float getVoxelSize() const { return state_.voxel_size; }
     ITMTrackingState* GetTrackingState() { return &tracking_state_; }
 
@@ -401,6 +480,8 @@ private:
     bool last_frame_fused_ = true;
     bool useApproximateRaycast = false;
     torch::Tensor fwd_block_, live_colour_;
+    torch::Tensor kf_raycast_, depth_colour_, depth_colour_scratch_;   // GetImage: kfRaycast (never written), DepthToUchar4's image and limits
+    torch::Tensor getImageSource(GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics);
     void* forwardBlock();   // the forward-render block when the option is on (allocated on first use), else NULL
     ITMTrackingState::TrackingResult verdictOfLastTrack() const;
     void ensureRelocaliser();

@@ -24,6 +24,38 @@ VOXEL_DT = np.dtype([("sdf", "<i2"), ("w_depth", "u1"), ("clr", "u1", (3,)), ("w
 HASH_DT = np.dtype([("pos", "<i2", (3,)), ("pad", "<i2"), ("offset", "<i4"), ("ptr", "<i4")])
 
 
+# ITMMainEngine::GetImageType (ITMLib/Core/ITMMainEngine.h:50-63)
+(InfiniTAM_IMAGE_ORIGINAL_RGB, InfiniTAM_IMAGE_ORIGINAL_DEPTH, InfiniTAM_IMAGE_SCENERAYCAST, InfiniTAM_IMAGE_COLOUR_FROM_VOLUME,
+ InfiniTAM_IMAGE_COLOUR_FROM_NORMAL, InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE, InfiniTAM_IMAGE_FREECAMERA_SHADED,
+ InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME, InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL,
+ InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE, InfiniTAM_IMAGE_UNKNOWN) = range(11)
+IMAGE_TYPE_NAMES = ("ORIGINAL_RGB", "ORIGINAL_DEPTH", "SCENERAYCAST", "COLOUR_FROM_VOLUME", "COLOUR_FROM_NORMAL", "COLOUR_FROM_CONFIDENCE",
+                    "FREECAMERA_SHADED", "FREECAMERA_COLOUR_FROM_VOLUME", "FREECAMERA_COLOUR_FROM_NORMAL",
+                    "FREECAMERA_COLOUR_FROM_CONFIDENCE", "UNKNOWN")
+# gps_render_type (include/gps_slam_hip.h)
+(RENDER_SHADED_GREYSCALE, RENDER_SHADED_GREYSCALE_IMAGENORMALS, RENDER_COLOUR_FROM_VOLUME, RENDER_COLOUR_FROM_NORMAL,
+ RENDER_COLOUR_FROM_CONFIDENCE) = range(5)
+# image type -> RenderImage pass (ITMBasicEngine.tpp:428-443, 473-479)
+_LIVE_RENDER = {InfiniTAM_IMAGE_SCENERAYCAST: RENDER_SHADED_GREYSCALE_IMAGENORMALS, InfiniTAM_IMAGE_COLOUR_FROM_VOLUME: RENDER_COLOUR_FROM_VOLUME,
+                InfiniTAM_IMAGE_COLOUR_FROM_NORMAL: RENDER_COLOUR_FROM_NORMAL, InfiniTAM_IMAGE_COLOUR_FROM_CONFIDENCE: RENDER_COLOUR_FROM_CONFIDENCE}
+_FREE_RENDER = {InfiniTAM_IMAGE_FREECAMERA_SHADED: RENDER_SHADED_GREYSCALE, InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME: RENDER_COLOUR_FROM_VOLUME,
+                InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL: RENDER_COLOUR_FROM_NORMAL,
+                InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_CONFIDENCE: RENDER_COLOUR_FROM_CONFIDENCE}
+
+
+def image_type_from(t):
+    """an InfiniTAM_IMAGE_* value, or its name with or without the prefix -> the value"""
+    if isinstance(t, str):
+        name = t[len("InfiniTAM_IMAGE_"):] if t.startswith("InfiniTAM_IMAGE_") else t
+        if name not in IMAGE_TYPE_NAMES:
+            raise ValueError("GetImage: unknown image type %r" % t)
+        return IMAGE_TYPE_NAMES.index(name)
+    t = int(t)
+    if not 0 <= t <= InfiniTAM_IMAGE_UNKNOWN:
+        raise ValueError("GetImage: image type %d out of range" % t)
+    return t
+
+
 def pose_from_c2w(c2w):
     """ORUtils::SE3Pose: SetInvM(c2w); Coerce(); -> (M, invM) as float32[16] in ORUtils layout (host only)."""
     c = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(4, 4))
@@ -51,6 +83,7 @@ class TsdfEngine:
         self.use_approximate_raycast = bool(use_approximate_raycast)
         self._fwd_block = None
         self._live_colour = None
+        self.relocalisationCount = 0   # (this mirror has no failure modes: GetImage's live types never answer kfRaycast)
         self.device = torch.device(device)
         self.voxel_size = float(voxel_size)
         d = self.device
@@ -281,6 +314,52 @@ class TsdfEngine:
     def GetLiveImage(self):
         """uchar4 [H,W,4] of the last runRaycast() without a pose"""
         return self._live_colour.view(self.H, self.W, 4)
+
+    # ---- ITMBasicEngine::GetImage (ITMBasicEngine.tpp:394-498)
+    def GetImage(self, image_type, c2w=None, pose=None, intrinsics=None):
+        """image_type: one of the InfiniTAM_IMAGE_* constants of this module, or its name (with or without the prefix).
+        -> uint8 [H, W, 4] device tensor of its own, written on the current stream; None before the first frame (view == NULL).
+        Live types: rendered from the last full cast while it is current (age_pointCloud <= 0), from the forward projection
+        afterwards, into the live render image (GetLiveImage()); SCENERAYCAST shades from the ray image's normals, the others from
+        the volume.  While relocalisationCount != 0 they answer kfRaycast, which the reference never writes: zeros.
+        Free-camera types: FindVisibleBlocks + CreateExpectedDepths + a cast that leaves the visible list alone at c2w / pose
+        (= (M, invM)), with intrinsics (fx, fy, cx, cy) or the depth camera's, into the free-view render state (GetFreeImage())."""
+        t = image_type_from(image_type)
+        if not self.camPoses:
+            return None
+        W, H, P = self.W, self.H, self.W * self.H
+        new = lambda: torch.zeros((H, W, 4), dtype=torch.uint8, device=self.device)
+        if t == InfiniTAM_IMAGE_ORIGINAL_RGB:
+            return self._frame_inputs[0].view(H, W, 4).clone()
+        if t == InfiniTAM_IMAGE_ORIGINAL_DEPTH:
+            if getattr(self, "_depth_scratch", None) is None:
+                self._depth_scratch = torch.zeros(int(lib.gps_tsdf_depth_to_rgba8_scratch_bytes()), dtype=torch.uint8, device=self.device)
+            out = new()
+            check(lib.gps_tsdf_depth_to_rgba8(self.depth.data_ptr(), P, self._depth_scratch.data_ptr(), out.data_ptr(), self._stream()),
+                  "gps_tsdf_depth_to_rgba8")
+            return out
+        if t in _LIVE_RENDER:
+            if self._live_colour is None:
+                self._live_colour = torch.zeros(P * 4, dtype=torch.uint8, device=self.device)
+            rays = self.raycast.data_ptr() if self.age_pointCloud <= 0 else self._fwd_block.data_ptr()
+            invM = self.camPoses[-1][1]
+            check(lib.gps_tsdf_render_image(C.byref(self.state), rays, W, H, invM.ctypes.data, _LIVE_RENDER[t], self._live_colour.data_ptr(),
+                                            self._stream()), "gps_tsdf_render_image")
+            if self.relocalisationCount != 0:   # kfRaycast: cleared at construction, never written (ITMBasicEngine.tpp:303, 357)
+                return new()
+            return self._live_colour.view(H, W, 4).clone()
+        if t in _FREE_RENDER:
+            if c2w is None and pose is None:
+                raise ValueError("GetImage: a free-camera image needs c2w or pose")
+            M, invM = pose if pose is not None else pose_from_c2w(c2w)
+            s = self.state
+            if intrinsics is not None:
+                s = TsdfState.from_buffer_copy(self.state)
+                s.fx, s.fy, s.cx, s.cy = (float(v) for v in intrinsics)
+            check(lib.gps_tsdf_get_image(C.byref(s), M.ctypes.data, invM.ctypes.data, _FREE_RENDER[t], None, self._stream()),
+                  "gps_tsdf_get_image")
+            return self.fv_colour.view(H, W, 4).clone()
+        return new()   # InfiniTAM_IMAGE_UNKNOWN: the cleared image
 
     def GetForwardProjection(self):
         """renderState->forwardProjection: float4 [H,W,4] of the last forward render (None before the option's first frame)"""

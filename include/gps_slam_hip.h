@@ -69,7 +69,9 @@ GPS_API const char *gps_build_flags(void);
 #define GPS_TIMED_RELOC_BLUR_CODE 10
 #define GPS_TIMED_RELOC_SEARCH 11
 #define GPS_TIMED_RELOC_FINISH 12
-#define GPS_TIMED_KINDS 13
+#define GPS_TIMED_RENDER_IMAGE 13   /* the shading kernels of gps_tsdf_render_image and gps_tsdf_depth_to_rgba8's colour pass */
+#define GPS_TIMED_RENDER_COLOUR 14  /* the colour-from-volume kernel through gps_tsdf_render_colour / _from (one view at a time) */
+#define GPS_TIMED_KINDS 15
 GPS_API int gps_launch_timing_start(int capacity);
 GPS_API int gps_launch_timing_stop(void);
 GPS_API int gps_launch_timing_read(int kind, double *total_us, int64_t *launches, double *total_us_flagged,
@@ -1115,6 +1117,41 @@ GPS_API int gps_tsdf_render_colour_from(const gps_tsdf_state *s, const float *ra
  * ts->age_point_cloud <= 0 and from the block's forward projection afterwards (fwd_block may be NULL in the first case). */
 GPS_API int gps_tsdf_render_live(const gps_tsdf_state *s, const gps_track_state *ts, const void *fwd_block, uint8_t *colour_out,
                                  gps_stream stream);
+
+/* ---- ITMBasicEngine::GetImage: the views of ITMVisualisationEngine::RenderImage and DepthToUchar4 (csrc/tsdf_image.hip) ------
+ * gps_tsdf_render_image: one RenderImage pass (ITMVisualisationEngine_CPU.tpp:239-332 without the raycast) over any ray image
+ * `rays` (float4 [height * width], voxel units, w > 0: found, w - 1: confidence) -> out_rgba8 (uchar4 [height * width]); a pixel
+ * that is not found, or whose normal faces away from the camera (!(angle > 0) against the light -column 2 of invM), is 0 0 0 0.
+ *   SHADED_GREYSCALE / COLOUR_FROM_NORMAL / COLOUR_FROM_CONFIDENCE   normal from the volume (computeSingleNormalFromSDF: 32 voxel
+ *                            reads through s->hash / s->vba), then drawPixelGrey / drawPixelNormal / drawPixelConfidence.
+ *                            drawPixelNormal leaves the destination's alpha alone in the reference; here a found pixel gets 255.
+ *   SHADED_GREYSCALE_IMAGENORMALS   normal from the ray image's +-2 neighbours, +-1 where one is missing or further than 0.15 m
+ *                            (processPixelGrey_ImageNormals<true, false>); reads s->voxel_size only.  Focal lengths of opposite
+ *                            sign (s->fx * s->fy < 0: the reference's flipNormals) are GPS_ERR_ARG.
+ *   COLOUR_FROM_VOLUME       the kernel of gps_tsdf_render_colour_from.
+ * width / height are the ray image's own (the volume types do not need the state's image size).  GPS_ERR_ARG before any launch
+ * for a NULL pointer, a size <= 0, an unknown type, and (volume types) a state without a valid scene.  No allocation, no sync. */
+typedef enum gps_render_type {
+    GPS_RENDER_SHADED_GREYSCALE = 0,
+    GPS_RENDER_SHADED_GREYSCALE_IMAGENORMALS = 1,
+    GPS_RENDER_COLOUR_FROM_VOLUME = 2,
+    GPS_RENDER_COLOUR_FROM_NORMAL = 3,
+    GPS_RENDER_COLOUR_FROM_CONFIDENCE = 4,
+    GPS_RENDER_N_TYPES = 5
+} gps_render_type;
+GPS_API int gps_tsdf_render_image(const gps_tsdf_state *s, const float *rays, int width, int height, const float *invM, int type,
+                                  uint8_t *out_rgba8, gps_stream stream);
+/* IITMVisualisationEngine::DepthToUchar4 (ITMVisualisationEngine.cpp:19-57): depth float[n] (device, metres, <= 0: invalid) in
+ * false colour -> out uchar4[n]; min and max over the valid depths are reduced on the device (scratch: device memory of
+ * gps_tsdf_depth_to_rgba8_scratch_bytes(), 8-byte aligned, any contents) and never reach the host.  All 0 when no depth is valid
+ * or min == max.  Three stream-ordered launches. */
+GPS_API int64_t gps_tsdf_depth_to_rgba8_scratch_bytes(void);
+GPS_API int gps_tsdf_depth_to_rgba8(const float *depth, int n, void *scratch, uint8_t *out_rgba8, gps_stream stream);
+/* GetImage's free-camera branch (ITMBasicEngine.tpp:468-494) in one call: gps_tsdf_free_raycast with a render type --
+ * find_visible + expected_depths(free) + raycast(free, the visible list untouched) + gps_tsdf_render_image over s->fv_raycast
+ * into out_rgba8 (s->fv_colour when NULL).  type: a volume type (not _IMAGENORMALS). */
+GPS_API int gps_tsdf_get_image(const gps_tsdf_state *s, const float *M, const float *invM, int type, uint8_t *out_rgba8,
+                               gps_stream stream);
 
 #ifdef __cplusplus
 }
