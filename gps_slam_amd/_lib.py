@@ -160,6 +160,8 @@ PROTOTYPES = {
     "gps_tsdf_depth_to_rgba8_scratch_bytes": (i64, []),
     "gps_tsdf_depth_to_rgba8": (i32, [vp, i32, vp, vp, vp]),
     "gps_tsdf_get_image": (i32, [C.POINTER(TsdfState), vp, vp, i32, vp, vp]),
+    "gps_tsdf_filter_scratch_bytes": (i64, [i32, i32]),
+    "gps_tsdf_convert_filter_depth": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_convert_depth": (i32, [C.POINTER(TsdfState), vp, vp]),
     "gps_tsdf_allocate": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_integrate": (i32, [C.POINTER(TsdfState), vp, vp]),

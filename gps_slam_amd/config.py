@@ -337,7 +337,7 @@ PIPE_KEYS = dict(max_iterations=_I, selected_cam_idx=_I, enable_densify=_B, eval
                  ssim_weight=_F, depth_weight=_F, color_error_max=_F, depth_error_max=_F, depth_vis_max=_F, depth_vis_min=_F,
                  alpha_vis_max=_F, sample_method=_S, loss_thres=_F, large_scale_thres=_F, small_scale_thres=_F, low_opac_thres=_F,
                  saved_mesh=_S, saved_engine=_S, saved_images=_S, voxel_size=_F, trunc_dist=_F, viewFrustum_min=_F,
-                 viewFrustum_max=_F, use_gt_pose=_B)
+                 viewFrustum_max=_F, use_gt_pose=_B, use_bilateral_filter=_B)
 READER_KEYS = dict(depth_scale=_F, scene_scale=_F, downscale_factor=_F, start_frame=_I, end_frame=_I, frame_step=_I,
                    test_split_interval=_I, input_dir=_S, image_path=_S, pose_path=_S, depth_path=_S, pcd_name=_S)
 

@@ -15,7 +15,8 @@ namespace gps {
 
 enum TimedKernel {   // == GPS_TIMED_* of include/gps_slam_hip.h
     TK_PREPROCESS_BWD = 0, TK_PREPROCESS_FWD, TK_RASTER_FWD, TK_RASTER_BWD_STRIPS, TK_SB_SCAN, TK_SB_SCATTER, TK_INTEGRATE, TK_RAYCAST,
-    TK_EXPOSURE, TK_RELOC_PYRAMID, TK_RELOC_BLUR_CODE, TK_RELOC_SEARCH, TK_RELOC_FINISH, TK_RENDER_IMAGE, TK_RENDER_COLOUR, TK_COUNT
+    TK_EXPOSURE, TK_RELOC_PYRAMID, TK_RELOC_BLUR_CODE, TK_RELOC_SEARCH, TK_RELOC_FINISH, TK_RENDER_IMAGE, TK_RENDER_COLOUR,
+    TK_FILTER_DEPTH, TK_COUNT
 };
 
 struct LaunchStamp { unsigned long long* slots; };   // {first start, last end} per WORKGROUP of one launch, or NULL

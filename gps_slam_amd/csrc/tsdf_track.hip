@@ -1529,7 +1529,7 @@ int gps_tsdf_process_frame_tracked(const gps_tsdf_state* s, const int16_t* depth
 // frame's visible list), then ITMTrackingController::Prepare at ts->pose.
 int gps_tsdf_frame_track(const gps_tsdf_state* s, const int16_t* depth_mm, const gps_track_config* cfg, gps_track_state* ts,
                          void* scratch, int64_t scratch_bytes, gps_stream stream) {
-    GPS_REQUIRE(s && depth_mm && cfg && ts);
+    GPS_REQUIRE(s && cfg && ts);   // (depth_mm == NULL: s->depth is the view's depth already -- gps_tsdf_convert_filter_depth)
     int r;
     if (ts->age_point_cloud != -1) {  // ITMTrackingState::HasValidPointCloud
         if (ts->age_point_cloud >= 0) ts->frames_processed++; else ts->frames_processed = 0;
@@ -1537,7 +1537,7 @@ int gps_tsdf_frame_track(const gps_tsdf_state* s, const int16_t* depth_mm, const
         const double t0 = wall_ms();
         if ((r = track_camera_impl(s, cfg, ts, scratch, scratch_bytes, stream, depth_mm)) != GPS_OK) return r;
         ts->diag[14] = (float)(wall_ms() - t0);   // host milliseconds in the tracker (launches + LM loop)
-    } else {
+    } else if (depth_mm) {
         if ((r = gps_tsdf_convert_depth(s, depth_mm, stream)) != GPS_OK) return r;
     }
     return GPS_OK;

@@ -417,6 +417,22 @@ PYBIND11_MODULE(_host, m) {
         t.configFields(reader);
         return t.use_approximate_raycast;
     });
+    m.def("tsdfConfigUseBilateralFilter", [](const gpsh::Node& tsdf_node) {
+        // the same for TSDF.use_bilateral_filter: the absent key is false, a value that is no boolean throws
+        TsdfConfig t;
+        const gpsh::Config c = gpsh::flattenNode(tsdf_node, "PIPE.TSDF", [&](auto& v) { t.configFields(v); });
+        gpsh::ConfigReader reader{c};
+        t.configFields(reader);
+        return t.use_bilateral_filter;
+    });
+    m.def("tsdfConfigUseBilateralFilterFlat", [](const py::dict& flat) {
+        // the flat route: the gpsh::Config createTsdfEngine(data_reader, config) reads (config.flatten's dict)
+        const gpsh::Config c = config_from_dict(flat);
+        TsdfConfig t;
+        gpsh::ConfigReader reader{c};
+        t.configFields(reader);
+        return t.use_bilateral_filter;
+    });
 
     // ---- TSDF engine
     py::class_<TsdfEngine>(m, "ITMBasicEngine")
@@ -509,6 +525,31 @@ PYBIND11_MODULE(_host, m) {
         // ---- approximate raycast (ITMLibSettings::useApproximateRaycast) and the live re-render, runRaycast(NULL, NULL)
         .def("setUseApproximateRaycast", &TsdfEngine::setUseApproximateRaycast)
         .def("usesApproximateRaycast", &TsdfEngine::usesApproximateRaycast)
+        .def("resetAll", &TsdfEngine::resetAll)
+        .def("setUseBilateralFilter", &TsdfEngine::setUseBilateralFilter)   // ITMLibSettings::useBilateralFilter
+        .def("usesBilateralFilter", &TsdfEngine::usesBilateralFilter)
+        .def("hasFilterScratch", &TsdfEngine::hasFilterScratch)
+        .def("stateTensors", [](TsdfEngine& e) {
+            // views (no copies) of the engine's device state under the names of gps_tsdf_state, for tests that digest it
+            const gps_tsdf_state& s = e.state();
+            const auto dev = e.counters().device();
+            const int64_t P = (int64_t)s.width * s.height, n_total = (int64_t)s.n_buckets + s.n_excess;
+            auto view = [&](void* p, int64_t n, torch::ScalarType t) {
+                return torch::from_blob(p, {n}, torch::TensorOptions().dtype(t).device(dev));
+            };
+            py::dict d;
+            d["vba"] = view(s.vba, (int64_t)s.n_blocks * 512 * 8, torch::kUInt8);
+            d["hash"] = view(s.hash, n_total * 16, torch::kUInt8);
+            d["counters"] = e.counters();
+            d["visible_type"] = view(s.visible_type, n_total, torch::kUInt8);
+            d["visible_ids"] = view(s.visible_ids, s.n_blocks, torch::kInt32);
+            d["depth"] = view(s.depth, P, torch::kFloat32);
+            d["minmax"] = view(s.minmax, P * 2, torch::kFloat32);
+            d["raycast"] = view(s.raycast, P * 4, torch::kFloat32);
+            d["icp_points"] = view(s.icp_points, P * 4, torch::kFloat32);
+            d["icp_normals"] = view(s.icp_normals, P * 4, torch::kFloat32);
+            return d;
+        })
         .def("agePointCloud", &TsdfEngine::agePointCloud)
         .def("runRaycast", [](TsdfEngine& e) { e.runRaycast(nullptr, nullptr); })
         .def("GetLiveImage", &TsdfEngine::GetLiveImage)

@@ -240,6 +240,8 @@ CLIEngine* createTsdfEngine(const DatasetReader& data_reader, const Config& conf
     dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine)->setFailureMode(internalSettings->behaviourOnFailure);
     internalSettings->useApproximateRaycast = tsdf.use_approximate_raycast;
     dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine)->setUseApproximateRaycast(internalSettings->useApproximateRaycast);
+    internalSettings->useBilateralFilter = tsdf.use_bilateral_filter;
+    dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine)->setUseBilateralFilter(internalSettings->useBilateralFilter);
     if (tsdf.use_gt_pose) {
         auto* be = dynamic_cast<ITMBasicEngine<ITMVoxel, ITMVoxelIndex>*>(mainEngine);
         be->turnOffTracking();

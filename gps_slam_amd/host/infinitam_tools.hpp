@@ -154,6 +154,7 @@ struct TsdfConfig {
     int sdf_local_block_num = -1, sdf_bucket_num = -1, sdf_excess_list_size = -1;
     std::string failure_mode = "ignore";   // ignore | stop_integration | relocalise (ITMLibSettings::behaviourOnFailure)
     bool use_approximate_raycast = false;  // ITMLibSettings::useApproximateRaycast
+    bool use_bilateral_filter = false;     // ITMLibSettings::useBilateralFilter
     template <class V> void configFields(V& v) {   // THE list of createTsdfEngine's keys (config_fields.hpp)
         v.f("voxel_size", voxel_size);
         v.f("trunc_dist", trunc_dist);
@@ -165,6 +166,7 @@ struct TsdfConfig {
         v.i("sdf_excess_list_size", sdf_excess_list_size, gpsh::kOptional);
         v.s("failure_mode", failure_mode, gpsh::kOptional);
         v.b("use_approximate_raycast", use_approximate_raycast, gpsh::kOptional);
+        v.b("use_bilateral_filter", use_bilateral_filter, gpsh::kOptional);
         for (const char* k : {"load_images", "saved_mesh", "saved_engine", "saved_images"}) v.ignored(k);   // (the pipeline's: SLAMPipeline::loadConfig)
     }
 };

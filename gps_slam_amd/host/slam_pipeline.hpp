@@ -428,7 +428,7 @@ void SLAMPipeline::configFields(V& v) {
         s.s("saved_images", saved_images);
         for (const char* k : {"voxel_size", "trunc_dist", "viewFrustum_min", "viewFrustum_max", "load_images", "use_gt_pose",
                               "sdf_local_block_num", "sdf_bucket_num", "sdf_excess_list_size", "failure_mode",
-                              "use_approximate_raycast"})
+                              "use_approximate_raycast", "use_bilateral_filter"})
             s.ignored(k);   // (createTsdfEngine's: TsdfConfig)
     }
     v.ignored("train_mode");     // (one of the two is in every shipped file; the render method is MODEL.render_method)

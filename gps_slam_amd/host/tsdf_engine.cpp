@@ -120,11 +120,13 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         if (!track_scratch_.defined()) turnOnTracking();  // ITMLibSettings defaults
         std::function<void()> gate;
         gate.swap(beforeNextFusion);
-        if (useApproximateRaycast) {   // the same two halves, Prepare with the forward render
-            check(gps_tsdf_frame_track(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_, track_scratch_.data_ptr(),
+        if (useBilateralFilter) filterDepth(depth_mm_i16);   // (the halves below then read state_.depth: depth_mm NULL)
+        if (useApproximateRaycast || useBilateralFilter) {   // the same two halves, Prepare with the forward render if asked to
+            check(gps_tsdf_frame_track(&state_, useBilateralFilter ? nullptr : ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_, track_scratch_.data_ptr(),
                                        track_scratch_.numel(), current_stream()), "gps_tsdf_frame_track");
             if (gate) gate();
-            check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 1, 0, forwardBlock(), 1, current_stream()), "gps_tsdf_frame_map_fwd");
+            check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 1, 0, forwardBlock(), useApproximateRaycast ? 1 : 0, current_stream()),
+                  "gps_tsdf_frame_map_fwd");
         } else {
             check(gps_tsdf_process_frame_tracked_gated(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_,
                                                        track_scratch_.data_ptr(), track_scratch_.numel(), current_stream(),
@@ -142,6 +144,12 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         pose_d_.SetInvM(c2w.data_ptr<float>());
         pose_d_.Coerce();
         if (beforeNextFusion) { std::function<void()> gate; gate.swap(beforeNextFusion); gate(); }
+        if (useBilateralFilter) {   // the filtered depth is in place: the rest of gps_tsdf_process_frame_fwd at the given pose
+            filterDepth(depth_mm_i16);
+            memcpy(track_state_.pose_M, pose_d_.GetM(), 64); memcpy(track_state_.pose_invM, pose_d_.GetInvM(), 64);
+            check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 1, 0, forwardBlock(), useApproximateRaycast ? 1 : 0, current_stream()),
+                  "gps_tsdf_frame_map_fwd");
+        } else
         // (gps_tsdf_process_frame's launches; Prepare runs with tracking off too -- ITMBasicEngine.tpp:355 -- and keeps the point
         // cloud's age and pose in the tracking state)
         check(gps_tsdf_process_frame_fwd(&state_, ptr<int16_t>(depth_mm_i16), pose_d_.GetM(), pose_d_.GetInvM(), &track_state_,
@@ -168,7 +176,15 @@ void TsdfEngine::ensureRelocaliser() {   // ITMBasicEngine.tpp:57-60
 void TsdfEngine::convertDepth(const torch::Tensor& depth_mm_i16) {
     TORCH_CHECK(depth_mm_i16.is_cuda() && depth_mm_i16.scalar_type() == torch::kInt16 && depth_mm_i16.is_contiguous() &&
                     depth_mm_i16.numel() == (int64_t)state_.width * state_.height, "depth must be a contiguous int16 [H,W] device tensor");
+    if (useBilateralFilter) return filterDepth(depth_mm_i16);
     check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), current_stream()), "gps_tsdf_convert_depth");
+}
+
+void TsdfEngine::filterDepth(const torch::Tensor& depth_mm_i16) {
+    TORCH_CHECK(depth_mm_i16.numel() == (int64_t)state_.width * state_.height, "depth must have the engine's image size");
+    if (!filter_scratch_.defined()) filter_scratch_ = zeros_bytes(gps_tsdf_filter_scratch_bytes(state_.width, state_.height), device_);
+    check(gps_tsdf_convert_filter_depth(&state_, ptr<int16_t>(depth_mm_i16), filter_scratch_.data_ptr(), current_stream()),
+          "gps_tsdf_convert_filter_depth");
 }
 
 // ITMBasicEngine.tpp:325-329: pose := the keyframe's; UpdateVisibleList(..., resetVisibleList = true) + Prepare there; TrackCamera
@@ -196,8 +212,9 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
     if (trackingActive) {
         if (!track_scratch_.defined()) turnOnTracking();
         const bool tracks = ts.age_point_cloud != -1;
-        check(gps_tsdf_frame_track(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &ts, track_scratch_.data_ptr(),
-                                   track_scratch_.numel(), st), "gps_tsdf_frame_track");
+        if (useBilateralFilter) filterDepth(depth_mm_i16);   // (frame_track then reads state_.depth: depth_mm NULL)
+        check(gps_tsdf_frame_track(&state_, useBilateralFilter ? nullptr : ptr<int16_t>(depth_mm_i16), &track_cfg_, &ts,
+                                   track_scratch_.data_ptr(), track_scratch_.numel(), st), "gps_tsdf_frame_track");
         if (tracks) {
             verdict = verdictOfLastTrack();
             tracked_frames_++;
@@ -209,7 +226,8 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
         auto c2w = gtC2wPoses[framesSeen].to(torch::kCPU, torch::kFloat32).contiguous();
         pose_d_.SetInvM(c2w.data_ptr<float>());
         memcpy(ts.pose_M, pose_d_.GetM(), 64); memcpy(ts.pose_invM, pose_d_.GetInvM(), 64);
-        check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), st), "gps_tsdf_convert_depth");
+        if (useBilateralFilter) filterDepth(depth_mm_i16);
+        else check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), st), "gps_tsdf_convert_depth");
     }
     const auto forced = forced_results_.find(framesSeen);
     if (forced != forced_results_.end()) verdict = forced->second;

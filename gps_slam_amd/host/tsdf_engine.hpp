@@ -139,6 +139,8 @@ public:
     FailureMode behaviourOnFailure = FAILUREMODE_IGNORE;
     // ITMLibSettings.h:45; the default is the reference's (ITMLibSettings.cpp:36).  TSDF.use_approximate_raycast of the configs.
     bool useApproximateRaycast = false;
+    // ITMLibSettings.h:47; the default is the reference's (ITMLibSettings.cpp:39).  TSDF.use_bilateral_filter of the configs.
+    bool useBilateralFilter = false;
     // TSDF.failure_mode of the configs: ignore | stop_integration | relocalise (anything else throws)
     static FailureMode failureModeFromString(const std::string& name) {
         if (name == "ignore") return FAILUREMODE_IGNORE;
@@ -323,6 +325,12 @@ public:
     // and casts rays for the empty pixels only; the tracker keeps aligning against the ICP maps of the full cast.
     void setUseApproximateRaycast(bool on) { useApproximateRaycast = on; }
     bool usesApproximateRaycast() const { return useApproximateRaycast; }
+    // ---- bilateral depth filter (ITMLibSettings::useBilateralFilter; gps_tsdf_convert_filter_depth): UpdateView runs five passes
+    // of the 5x5 depth-adaptive filter behind the conversion, so tracking, allocation, integration, the relocaliser and GetImage's
+    // original-depth view all see the filtered image (its two outer rows and columns are 0: invalid).  Off: today's launches.
+    void setUseBilateralFilter(bool on) { useBilateralFilter = on; }
+    bool usesBilateralFilter() const { return useBilateralFilter; }
+    bool hasFilterScratch() const { return filter_scratch_.defined(); }   // (allocated by the option's first frame only)
     int agePointCloud() const { return track_state_.age_point_cloud; }
     torch::Tensor GetForwardProjection() const;   // renderState->forwardProjection, float [H,W,4] (undefined before the first use)
     torch::Tensor GetLiveImage() const { return live_colour_; }   // uchar4 [H,W,4] of the last runRaycast(NULL, NULL)
@@ -479,6 +487,9 @@ private:
     std::unique_ptr<FernRelocLib::Relocaliser<float>> relocaliser_;
     bool last_frame_fused_ = true;
     bool useApproximateRaycast = false;
+    bool useBilateralFilter = false;
+    torch::Tensor filter_scratch_;
+    void filterDepth(const torch::Tensor& depth_mm_i16);   // UpdateView with the filter: conversion + five passes into state_.depth
     torch::Tensor fwd_block_, live_colour_;
     torch::Tensor kf_raycast_, depth_colour_, depth_colour_scratch_;   // GetImage: kfRaycast (never written), DepthToUchar4's image and limits
     torch::Tensor getImageSource(GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics);

@@ -77,8 +77,12 @@ class TsdfEngine:
 
     def __init__(self, width, height, fx, fy, cx, cy, voxel_size=0.005, mu=0.02, view_frustum_min=0.2,
                  view_frustum_max=10.0, n_blocks=SDF_LOCAL_BLOCK_NUM, n_buckets=SDF_BUCKET_NUM,
-                 n_excess=SDF_EXCESS_LIST_SIZE, device="cuda:0", use_approximate_raycast=False):
+                 n_excess=SDF_EXCESS_LIST_SIZE, device="cuda:0", use_approximate_raycast=False,
+                 use_bilateral_filter=False):
         self.W, self.H = int(width), int(height)
+        # ITMLibSettings::useBilateralFilter: UpdateView runs five passes of the bilateral depth filter behind the conversion
+        self.use_bilateral_filter = bool(use_bilateral_filter)
+        self._filter_scratch = None
         # ITMLibSettings::useApproximateRaycast: Prepare forward-projects the last full cast while the camera stays close to it
         self.use_approximate_raycast = bool(use_approximate_raycast)
         self._fwd_block = None
@@ -150,6 +154,14 @@ class TsdfEngine:
             self._fwd_block = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
         return self._fwd_block.data_ptr()
 
+    def _filter_depth(self, depth_mm_i16):
+        """UpdateView with useBilateralFilter: conversion + five filter passes into the state's depth (gps_tsdf_convert_filter_depth)"""
+        if self._filter_scratch is None:
+            nbytes = int(lib.gps_tsdf_filter_scratch_bytes(self.W, self.H))
+            self._filter_scratch = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        check(lib.gps_tsdf_convert_filter_depth(C.byref(self.state), depth_mm_i16.data_ptr(), self._filter_scratch.data_ptr(),
+                                                self._stream()), "gps_tsdf_convert_filter_depth")
+
     # ---- ITMBasicEngine::ProcessFrame (tracking off: pose := gtC2wPoses[framesProcessed]; Coerce())
     def ProcessFrame(self, rgb_u8, depth_mm_i16, gt_c2w):
         """rgb_u8: uint8 [H,W,4] device tensor (uchar4, as ITMUChar4Image; [H,W,3] is padded with a copy);
@@ -161,6 +173,14 @@ class TsdfEngine:
         self._frame_inputs = (rgb_u8, depth_mm_i16)  # keep alive while kernels may read them
         self.state.rgb = rgb_u8.data_ptr()
         M, invM = pose_from_c2w(gt_c2w)
+        if self.use_bilateral_filter:   # the filtered depth is in place: the rest of gps_tsdf_process_frame_fwd at the given pose
+            self._filter_depth(depth_mm_i16)
+            self.track_state.pose_M[:] = M.tolist(); self.track_state.pose_invM[:] = invM.tolist()
+            check(lib.gps_tsdf_frame_map_fwd(C.byref(self.state), C.byref(self.track_state), 1, 0, self._forward_block(),
+                                             1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_frame_map_fwd")
+            self.camPoses.append((M, invM))
+            self.frames_processed += 1
+            return M, invM
         # (gps_tsdf_process_frame's launches; Prepare keeps the point cloud's age and pose, and forward-renders if asked to)
         check(lib.gps_tsdf_process_frame_fwd(C.byref(self.state), depth_mm_i16.data_ptr(), M.ctypes.data, invM.ctypes.data,
                                              C.byref(self.track_state), self._forward_block(),
@@ -215,7 +235,14 @@ class TsdfEngine:
         assert rgb_u8.is_contiguous() and depth_mm_i16.is_contiguous()
         self._frame_inputs = (rgb_u8, depth_mm_i16)
         self.state.rgb = rgb_u8.data_ptr()
-        if self.use_approximate_raycast:   # the two halves of gps_tsdf_process_frame_tracked, Prepare with the forward render
+        if self.use_bilateral_filter:   # the two halves again, the tracker reading the filtered depth (depth_mm NULL)
+            self._filter_depth(depth_mm_i16)
+            check(lib.gps_tsdf_frame_track(C.byref(self.state), None, C.byref(self.track_cfg),
+                                           C.byref(self.track_state), self.track_scratch.data_ptr(), self.track_scratch.numel(),
+                                           self._stream()), "gps_tsdf_frame_track")
+            check(lib.gps_tsdf_frame_map_fwd(C.byref(self.state), C.byref(self.track_state), 1, 0, self._forward_block(),
+                                             1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_frame_map_fwd")
+        elif self.use_approximate_raycast:   # the two halves of gps_tsdf_process_frame_tracked, Prepare with the forward render
             check(lib.gps_tsdf_frame_track(C.byref(self.state), depth_mm_i16.data_ptr(), C.byref(self.track_cfg),
                                            C.byref(self.track_state), self.track_scratch.data_ptr(), self.track_scratch.numel(),
                                            self._stream()), "gps_tsdf_frame_track")

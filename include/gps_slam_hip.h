@@ -71,7 +71,8 @@ GPS_API const char *gps_build_flags(void);
 #define GPS_TIMED_RELOC_FINISH 12
 #define GPS_TIMED_RENDER_IMAGE 13   /* the shading kernels of gps_tsdf_render_image and gps_tsdf_depth_to_rgba8's colour pass */
 #define GPS_TIMED_RENDER_COLOUR 14  /* the colour-from-volume kernel through gps_tsdf_render_colour / _from (one view at a time) */
-#define GPS_TIMED_KINDS 15
+#define GPS_TIMED_FILTER_DEPTH 15   /* the five passes of gps_tsdf_convert_filter_depth */
+#define GPS_TIMED_KINDS 16
 GPS_API int gps_launch_timing_start(int capacity);
 GPS_API int gps_launch_timing_stop(void);
 GPS_API int gps_launch_timing_read(int kind, double *total_us, int64_t *launches, double *total_us_flagged,
@@ -1066,7 +1067,9 @@ GPS_API int gps_tsdf_process_frame_tracked_gated(const gps_tsdf_state *s, const 
  * gps_tsdf_process_frame_tracked_gated is frame_track, the hook, frame_map(fuse = 1).
  * gps_tsdf_update_visible_list: the allocation sweep of gps_tsdf_allocate with allocation suppressed (AllocateSceneFromDepth's
  * onlyUpdateVisibleList) -- existing blocks inside the depth band are marked visible, last frame's visible blocks are re-tested
- * against the frustum (reset_visible != 0: dropped instead), no block is allocated and no counter but N_VISIBLE changes. */
+ * against the frustum (reset_visible != 0: dropped instead), no block is allocated and no counter but N_VISIBLE changes.
+ * gps_tsdf_frame_track with depth_mm == NULL: s->depth already IS the view's depth (gps_tsdf_convert_filter_depth wrote it);
+ * nothing is converted.  With a depth image the call is what it always was. */
 GPS_API int gps_tsdf_update_visible_list(const gps_tsdf_state *s, const float *M, const float *invM, int reset_visible,
                                          gps_stream stream);
 GPS_API int gps_tsdf_frame_track(const gps_tsdf_state *s, const int16_t *depth_mm, const gps_track_config *cfg, gps_track_state *ts,
@@ -1152,6 +1155,19 @@ GPS_API int gps_tsdf_depth_to_rgba8(const float *depth, int n, void *scratch, ui
  * into out_rgba8 (s->fv_colour when NULL).  type: a volume type (not _IMAGENORMALS). */
 GPS_API int gps_tsdf_get_image(const gps_tsdf_state *s, const float *M, const float *invM, int type, uint8_t *out_rgba8,
                                gps_stream stream);
+
+/* ---- ITMLibSettings::useBilateralFilter: UpdateView's depth conversion + five passes of filterDepth (csrc/tsdf_view.hip) ----
+ * depth_mm int16[H*W] (device, millimetres) -> s->depth: ConvertDepthAffineToFloat as gps_tsdf_convert_depth does it, then
+ * DepthFiltering five times (ITMViewBuilder_CPU.cpp:53-62; ViewBuilding/Shared/ITMViewBuilder_Shared.h:38-67), the reference's
+ * fp32 sequence with the exponential computed in double and rounded once.  The two outer rows and columns of the result are
+ * 0.0f (every pass clears its output and filters the interior only), an invalid pixel stays -1; an image narrower or lower
+ * than 5 pixels ends as all zeros.  scratch: device memory of gps_tsdf_filter_scratch_bytes(width, height) (two float images),
+ * 4-byte aligned, any contents.  Reads of the state: width, height, depth.  Five stream-ordered launches, no allocation, no
+ * sync.  GPS_ERR_ARG before any launch for a NULL or misaligned pointer or a size <= 0 (the size function: < 0).
+ * A frame with the option on: this call, then the frame's entry points with the depth in place -- gps_tsdf_frame_track with
+ * depth_mm == NULL, gps_tsdf_frame_map_fwd, gps_tsdf_track_camera. */
+GPS_API int64_t gps_tsdf_filter_scratch_bytes(int width, int height);
+GPS_API int gps_tsdf_convert_filter_depth(const gps_tsdf_state *s, const int16_t *depth_mm, void *scratch, gps_stream stream);
 
 #ifdef __cplusplus
 }
