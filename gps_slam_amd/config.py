@@ -337,9 +337,29 @@ PIPE_KEYS = dict(max_iterations=_I, selected_cam_idx=_I, enable_densify=_B, eval
                  ssim_weight=_F, depth_weight=_F, color_error_max=_F, depth_error_max=_F, depth_vis_max=_F, depth_vis_min=_F,
                  alpha_vis_max=_F, sample_method=_S, loss_thres=_F, large_scale_thres=_F, small_scale_thres=_F, low_opac_thres=_F,
                  saved_mesh=_S, saved_engine=_S, saved_images=_S, voxel_size=_F, trunc_dist=_F, viewFrustum_min=_F,
-                 viewFrustum_max=_F, use_gt_pose=_B, use_bilateral_filter=_B)
+                 viewFrustum_max=_F, use_gt_pose=_B, use_bilateral_filter=_B,
+                 refine_iterations=_I, refine_cams=_S, refine_seed=_I, refine_cache_mb=_I)
 READER_KEYS = dict(depth_scale=_F, scene_scale=_F, downscale_factor=_F, start_frame=_I, end_frame=_I, frame_step=_I,
                    test_split_interval=_I, input_dir=_S, image_path=_S, pose_path=_S, depth_path=_S, pcd_name=_S)
+
+
+def refine_settings(pipe_section):
+    """This project's optional PIPE keys of the refinement pass (host/slam_pipeline.hpp configFields): refine_iterations (0: off),
+    refine_cams ('keyframes' or 'all'), refine_seed (None: the pipeline's seed), refine_cache_mb.  A bad value raises a
+    ConfigError that carries the key's path."""
+    def get(key, convert, default):
+        v = pipe_section.get(key)
+        return default if v is None else convert(v)
+    out = dict(refine_iterations=get("refine_iterations", _I, 0), refine_cams=get("refine_cams", _S, "keyframes"),
+               refine_seed=get("refine_seed", _I, None), refine_cache_mb=get("refine_cache_mb", _I, 16384))
+    if out["refine_cams"] not in ("keyframes", "all"):
+        v = pipe_section["refine_cams"]
+        raise ConfigError("%s: 'keyframes' or 'all', got '%s'" % (getattr(v, "path", "PIPE.refine_cams"), out["refine_cams"]),
+                          getattr(v, "line", 0))
+    if out["refine_iterations"] < 0:
+        v = pipe_section["refine_iterations"]
+        raise ConfigError("%s: must not be negative" % getattr(v, "path", "PIPE.refine_iterations"), getattr(v, "line", 0))
+    return out
 
 
 def flatten(section, keys=None):

@@ -259,6 +259,14 @@ def compute_quat(init_vec, target_vec):
     return torch.cat([torch.cos(half), naxis * torch.sin(half)], 1)
 
 
+def scheduler_gamma(max_iterations):
+    """The decay factor of the means' rate, None without a scheduler: std::pow(0.01, 1.0f / max_iterations) as the reference writes
+    it (raw_gs_model.cpp:673-674) -- the quotient in float, widened, then a double pow"""
+    if max_iterations <= 0:
+        return None
+    return math.pow(0.01, float(np.float32(1.0) / np.float32(max_iterations)))
+
+
 class RawGaussianModel:
     def __init__(self, cfg=None, device="cuda:0"):
         cfg = dict(cfg or {})
@@ -270,6 +278,7 @@ class RawGaussianModel:
         self.delta_depth = cfg.get("delta_depth", 0.1)
         self.maxSH = cfg.get("sh_degree", 3)
         self.degreesToUse = self.maxSH
+        self.shDegreeInterval = cfg.get("sh_degree_interval", 0)
         self.maxInitScale = cfg.get("max_init_scale", 0.01)
         self.minInitScale = cfg.get("min_init_scale", -1)
         self.defaultOpacities = cfg.get("default_opacities", 0.5)
@@ -286,6 +295,7 @@ class RawGaussianModel:
         # sorted-key binning + 32-pixel-group kernel of the operator-level entry points
         self.strip_backward = bool(cfg.get("strip_backward", True))
         self._opt = None       # Adam state: capacity-sized m / v / g buffers + step count
+        self._gamma = None     # decay factor of the means' rate per schedulersStep() (initOptimizers with max_iterations > 0)
         self._step = None      # persistent gps_splat_step
         self._step_key = None
         self._B = None         # capacity-sized intermediates the step struct points at
@@ -345,6 +355,7 @@ class RawGaussianModel:
             self._step, self._step_key, self._B = st, key, B
         st = self._step
         st.N = p.N
+        st.sh_degree = self.degreesToUse   # (updateSH may have changed it since the struct was made)
         for name, src in (("means", "means"), ("log_scales", "scales"), ("quats", "quats"), ("opac_logit", "opacities"),
                           ("sh_dc", "featuresDc"), ("sh_rest", "featuresRest")):
             setattr(st, name, p._buf[src].data_ptr())
@@ -415,6 +426,13 @@ class RawGaussianModel:
             e["v"][e["rows"]:F] = 0
         return e
 
+    def updateSH(self, curr_iter=-1):
+        """raw_gs_model.h:26-32: the SH degree in use grows by one every sh_degree_interval iterations"""
+        if curr_iter >= 0 and self.shDegreeInterval > 0:
+            self.degreesToUse = min(self.maxSH, curr_iter // self.shDegreeInterval)
+        else:
+            self.degreesToUse = self.maxSH
+
     @staticmethod
     def clamp_ref_depth(ref_depth):
         """ref_depth_clamped = where(ref < 0.01, 1000, ref) (raw_gs_model.cpp:205-207)"""
@@ -455,10 +473,26 @@ class RawGaussianModel:
         # (an existing state is NOT zeroed: step 1 of gps_splat_train_step / gps_adam_step takes the moments as zero without reading
         # them and writes every live row -- include/gps_slam_hip.h, gps_adam_step)
         self._opt.update(lrs=lrs, step=0)
+        # meansOptScheduler (raw_gs_model.cpp:673-674): gamma = std::pow(0.01, 1.0f / max_iterations), a float quotient and a double pow
+        self._gamma = scheduler_gamma(max_iterations)
         # exposureOpt (raw_gs_model.cpp:672): own state and step count
         e = self._exp or dict(m=None, v=None, g=None, slab=None)
         e.update(lr=float(f32(self.exposure_lr)), step=0, rows=0)
         self._exp = e
+
+    def schedulersStep(self):
+        """raw_gs_model.h:167-173: lr *= gamma for the means (include/optim_scheduler.hpp); nothing without a scheduler"""
+        if self._gamma is not None:
+            self._opt["lrs"][0] = self._opt["lrs"][0] * self._gamma
+
+    def hasScheduler(self):
+        return getattr(self, "_gamma", None) is not None
+
+    def meansLr(self):
+        return self._opt["lrs"][0]
+
+    def adamStep(self):
+        return self._opt["step"]
 
     def grads(self):
         """parameter gradients of the last train_step, NAMES order ([:N] views)"""
@@ -484,14 +518,14 @@ class RawGaussianModel:
         st = self._step_struct(cam.width, cam.height)
         c = cam.toGPU()
         ver = self.opt_gs_params.version
-        key = (c["serial"], int(st.N), cam.width, cam.height, ver)
+        key = (c["serial"], int(st.N), cam.width, cam.height, ver, int(st.sh_degree))   # (the degree of THIS step)
         skip = getattr(self, "_prefetched", None) == key
         self._bind_camera(st, cam, ref_depth_clamped, base_color, gt_rgb, consumes_prefetch=skip)
         st.preprocessed = 1 if skip else 0
         if next_cam is not None and (next_cam.width, next_cam.height) == (cam.width, cam.height) and lib.gps_splat_can_prefetch(C.byref(st)):
             n = next_cam.toGPU()
             st.next_viewmat, st.next_Kmat, st.next_cam_pos = n["viewmat"].data_ptr(), n["K"].data_ptr(), n["cam_pos"].data_ptr()
-            armed = (n["serial"], int(st.N), cam.width, cam.height, ver)
+            armed = (n["serial"], int(st.N), cam.width, cam.height, ver, int(st.sh_degree))
         else:
             armed = None
         o = self._opt

@@ -48,6 +48,13 @@ struct FieldDumper {
     void s(const char* k, std::string& v, gpsh::FieldUse = gpsh::kRequired) { put(k, v); }
     void ignored(const char*) {}
 };
+// gpsh::RandomSelector points into its items: the Python object holds them
+struct PySelector {
+    std::vector<int64_t> items;
+    gpsh::RandomSelector<int64_t> sel;
+    PySelector(std::vector<int64_t> v, uint64_t seed) : items(std::move(v)), sel(items, seed) {}
+    PySelector(const PySelector&) = delete;
+};
 }  // namespace
 
 PYBIND11_MODULE(_host, m) {
@@ -224,6 +231,14 @@ PYBIND11_MODULE(_host, m) {
         .def("lossTerms", &SLAMGaussianModel::lossTerms)
         .def("initOptimizers", &SLAMGaussianModel::initOptimizers, py::arg("max_iterations") = -1,
              py::arg("scene_scale") = 1.0f)
+        .def("schedulersStep", &SLAMGaussianModel::schedulersStep)
+        .def("hasScheduler", &SLAMGaussianModel::hasScheduler)
+        .def("meansLr", &SLAMGaussianModel::meansLr)
+        .def("adamStep", &SLAMGaussianModel::adamStep)
+        .def("updateSH", &SLAMGaussianModel::updateSH, py::arg("curr_iter") = -1)
+        .def_readwrite("maxSH", &SLAMGaussianModel::maxSH)
+        .def_readwrite("shDegreeInterval", &SLAMGaussianModel::shDegreeInterval)
+        .def_readonly("degreesToUse", &SLAMGaussianModel::degreesToUse)
         .def("optimizersStep", &SLAMGaussianModel::optimizersStep)
         .def("optimizersZeroGrad", &SLAMGaussianModel::optimizersZeroGrad)
         .def("prunePoints", &SLAMGaussianModel::prunePoints)
@@ -240,6 +255,19 @@ PYBIND11_MODULE(_host, m) {
         .def("getRealOpacities", &SLAMGaussianModel::getRealOpacities)
         .def("addGaussians", [](SLAMGaussianModel& s, const Camera& cam, const TensorDict& maps, const torch::Tensor& mask,
                                 float ratio, int frame_num) { return s.addGaussians(cam, maps, mask, ratio, frame_num); });
+
+    // ---- gpsh::RandomSelector / gpsh::OptimScheduler (random_selector.hpp): host code, no device
+    py::class_<PySelector>(m, "RandomSelector")
+        .def(py::init<std::vector<int64_t>, uint64_t>(), py::arg("items"), py::arg("seed"))
+        .def("getNext", [](PySelector& s) {
+            const auto e = s.sel.getNext();
+            return std::make_pair(*e.value, e.originalIndex);   // (value, originalIndex)
+        });
+    py::class_<gpsh::OptimScheduler>(m, "OptimScheduler")
+        .def(py::init<int>(), py::arg("max_iterations"))
+        .def_readonly("active", &gpsh::OptimScheduler::active)
+        .def_readonly("gamma", &gpsh::OptimScheduler::gamma)
+        .def("step", [](const gpsh::OptimScheduler& s, double lr) { s.step(lr); return lr; }, py::arg("lr"));
 
     // ---- geometry / trajectory evaluation (geom_eval.hpp)
     py::class_<GeomEvalResult>(m, "GeomEvalResult")
@@ -778,6 +806,28 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("gt_points_or_triangles"), py::arg("transform") = py::none(), py::arg("dist_thres") = std::vector<double>{0.03},
              py::arg("sample_nums") = 1000000, py::arg("seed") = 0)
         .def("evalTrajectory", &SLAMPipeline::evalTrajectory, py::call_guard<py::gil_scoped_release>())
+        .def("gesTrainCams", [](SLAMPipeline& p, const std::vector<Camera>& cams, int max_iterations, int64_t seed) {
+            return p.gesTrainCams(cams, max_iterations, seed);
+        }, py::arg("cams"), py::arg("max_iterations") = -1, py::arg("seed") = -1, py::call_guard<py::gil_scoped_release>())
+        .def("gesTrainCamsWithLayers", [](SLAMPipeline& p, const std::vector<Camera>& cams, const std::vector<TensorDict>& layers, int max_iterations,
+                                          int64_t seed) { return p.gesTrainCams(cams, layers, max_iterations, seed); },
+             py::arg("cams"), py::arg("base_layers"), py::arg("max_iterations") = -1, py::arg("seed") = -1, py::call_guard<py::gil_scoped_release>())
+        .def("refineKeyframeCams", [](SLAMPipeline& p) { { py::gil_scoped_release nogil; p.flush(); } return p.refineKeyframeCams(); })
+        .def("refineCacheBytes", &SLAMPipeline::refineCacheBytes, py::arg("cams"))
+        .def("refineLog", [](SLAMPipeline& p) {
+            std::vector<std::pair<int, float>> out;
+            for (const auto& e : p.refine_log) out.emplace_back(e.iter, e.loss);
+            return out;
+        })
+        .def_readwrite("curr_iter", &SLAMPipeline::curr_iter)
+        .def_readwrite("max_iterations", &SLAMPipeline::max_iterations)
+        .def_readwrite("selected_cam_idx", &SLAMPipeline::selected_cam_idx)
+        .def_readwrite("log_iter", &SLAMPipeline::log_iter)
+        .def_readwrite("refine_iterations", &SLAMPipeline::refine_iterations)
+        .def_readwrite("refine_cams", &SLAMPipeline::refine_cams)
+        .def_readwrite("refine_seed", &SLAMPipeline::refine_seed)
+        .def_readwrite("refine_cache_mb", &SLAMPipeline::refine_cache_mb)
+        .def_readwrite("refine_lr_decay", &SLAMPipeline::refine_lr_decay)
         .def("evalImages", &SLAMPipeline::evalImages, py::arg("cams"), py::arg("depth_mask") = false, py::arg("source") = "rgb",
              py::call_guard<py::gil_scoped_release>())
         .def("saveMesh", &SLAMPipeline::saveMesh)
@@ -794,6 +844,12 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("has_image_eval", &SessionResult::has_image_eval)
         .def_readonly("keyframe_count", &SessionResult::keyframe_count)
         .def_readonly("gaussian_num", &SessionResult::gaussian_num)
+        .def_readonly("refine_iterations_done", &SessionResult::refine_iterations_done)
+        .def_property_readonly("refine_log", [](const SessionResult& r) {
+            std::vector<std::pair<int, float>> out;
+            for (const auto& e : r.refine_log) out.emplace_back(e.iter, e.loss);
+            return out;
+        })
         .def_readonly("times", &SessionResult::times)
         .def_readonly("files", &SessionResult::files);
     m.def("run_session", &runSession, py::arg("root"), py::arg("reader"), py::arg("config_filename") = "",

@@ -460,7 +460,6 @@ std::vector<torch::Tensor> RawGaussianModel::exposureAdamState() {
 }
 
 void RawGaussianModel::initOptimizers(int max_iterations, float scene_scale) {
-    (void)max_iterations;
     RawGaussianParams& p = opt_gs_params;
     const int64_t cap = p.capacity();
     if (!have_opt_ || adam_cap_ != cap) {
@@ -482,6 +481,7 @@ void RawGaussianModel::initOptimizers(int max_iterations, float scene_scale) {
     lrs_[0] = (double)((float)means_lr * scene_scale); lrs_[1] = (double)(float)scales_lr; lrs_[2] = (double)(float)quats_lr;
     lrs_[3] = (double)(float)featuresDc_lr; lrs_[4] = (double)(float)featuresRest_lr; lrs_[5] = (double)(float)opacities_lr;
     adam_step_ = 0;
+    means_scheduler_ = OptimScheduler(max_iterations);   // raw_gs_model.cpp:673-674
     // exposureOpt (raw_gs_model.cpp:672): its own state and step count, lr widened from the float member like the others
     exp_lr_ = (double)(float)exposure_lr;
     exp_step_ = 0;
@@ -496,9 +496,11 @@ void RawGaussianModel::reserveWorkspace(int width, int height) {
     const bool had = have_opt_;
     const int step = adam_step_, exp_step = exp_step_;
     const int64_t exp_rows = exp_state_rows_;
+    const OptimScheduler scheduler = means_scheduler_;
     initOptimizers(-1, 1.0f);  // allocates m / v / g at capacity
     have_opt_ = had;           // ... but leaves the optimiser logically un-initialised if it was
     adam_step_ = step;
+    means_scheduler_ = scheduler;
     exp_step_ = exp_step; exp_state_rows_ = exp_rows;
 }
 
@@ -556,7 +558,8 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
     auto clamped = ref_depth_clamped.defined() ? ref_depth_clamped : clampRefDepth(ref_depth);
     gps_splat_step& st = stepStruct(cam.width, cam.height);
     // did the previous trainStep() run this camera's preprocessing forward in its backward kernel's tail (next_cam)?
-    const PrefetchKey mine{cam.pack_serial(), (int64_t)st.N, cam.width, cam.height, opt_gs_params.version()};
+    // (with the SH degree of THIS step: the forward run ahead was evaluated with the previous step's)
+    const PrefetchKey mine{cam.pack_serial(), (int64_t)st.N, cam.width, cam.height, opt_gs_params.version(), (int)st.sh_degree};
     const bool skip = prefetched_.camera != 0 && prefetched_ == mine;
     bindCamera(st, cam, clamped, base_color, cam.image, skip);   // (clears prefetched_)
     st.fuse_sh_rest_adam = fuse_sh_rest_adam ? 2 : 0;  // all six tensors stepped inside the backward kernel
@@ -604,7 +607,7 @@ void RawGaussianModel::trainStep(const Camera& cam, const torch::Tensor& ref_dep
     st.ssim_weight = st.depth_weight = 0.f;
     check(rc, "gps_splat_train_step");   // throws on error: nothing armed then
     if (row >= 0) { exp_step_ += 1; exp_state_rows_ = opt_gs_params.exposureRows(); }
-    if (ahead) prefetched_ = PrefetchKey{next_cam->pack_serial(), (int64_t)st.N, cam.width, cam.height, opt_gs_params.version()};
+    if (ahead) prefetched_ = PrefetchKey{next_cam->pack_serial(), (int64_t)st.N, cam.width, cam.height, opt_gs_params.version(), (int)st.sh_degree};
     nextLaunchId();
 }
 

@@ -9,6 +9,7 @@
 //     autograd graph) -- what SLAMPipeline::localOptimize uses.
 #pragma once
 #include "config_fields.hpp"
+#include "random_selector.hpp"
 #include "raw_gs_param.hpp"
 
 class RawGaussianModel {
@@ -72,7 +73,15 @@ public:
     // Overflow since the last check -> throws (Gaussians were dropped from a render / backward); more than half of a
     // capacity in use -> the buffers are doubled before the next iteration.  Returns {n_isects, n_groups} of the last launch.
     std::pair<int64_t, int64_t> checkBinningCapacity();
-    void initOptimizers(int max_iterations = -1, float scene_scale = 1);  // raw_gs_model.cpp:654-675
+    // raw_gs_model.cpp:654-675.  max_iterations > 0: the means' rate decays to 0.01 x its start over that many schedulersStep()
+    // calls (meansOptScheduler, gpsh::OptimScheduler); <= 0: constant rates
+    void initOptimizers(int max_iterations = -1, float scene_scale = 1);
+    // raw_gs_model.h:167-173: one step of the means' scheduler (nothing without one).  The next trainStep() / optimizersStep() is
+    // handed the new rate the way the constant one is: lrs_[0] through the step struct / the Adam segment
+    void schedulersStep() { means_scheduler_.step(lrs_[0]); }
+    bool hasScheduler() const { return means_scheduler_.active; }
+    double meansLr() const { return lrs_[0]; }
+    int adamStep() const { return adam_step_; }
     void optimizersZeroGrad();
     void optimizersStep();
     void prunePoints(const torch::Tensor& deleteMask);  // raw_gs_model.cpp:635-644 (+ removeFromOptimizer)
@@ -175,8 +184,9 @@ public:
         int64_t N = 0;
         int W = 0, H = 0;
         uint64_t version = 0;  // RawGaussianParams::version(): an add / prune between the two steps voids the forward run ahead
+        int sh_degree = -1;    // the degree the colours were evaluated with: an updateSH() between the two steps voids it as well
         bool operator==(const PrefetchKey& o) const {
-            return camera == o.camera && N == o.N && W == o.W && H == o.H && version == o.version;
+            return camera == o.camera && N == o.N && W == o.W && H == o.H && version == o.version && sh_degree == o.sh_degree;
         }
     };
     PrefetchKey prefetched_;
@@ -190,6 +200,7 @@ protected:
     // Adam state: capacity-sized exp_avg / exp_avg_sq / grad buffers in reference parameter order + step count
     std::vector<torch::Tensor> adam_m_, adam_v_, adam_g_;
     double lrs_[RawGaussianParams::NUM] = {0, 0, 0, 0, 0, 0};
+    gpsh::OptimScheduler means_scheduler_;
     int64_t adam_cap_ = -1;
     int adam_step_ = 0;
     bool have_opt_ = false;

@@ -260,6 +260,12 @@ SessionResult runSession(const Node& root, DatasetReader& reader, const std::str
         pipe.SLAMTrainCams(model, reader.train_vec);
         res.times = pipe.times;
         res.keyframe_count = (int)pipe.keyframe_cam_list.size();
+        if (pipe.refine_iterations > 0 && res.work_mode == "train") {
+            // the pass over all keyframes (or all cameras) once the sequence is over, before anything is saved or rendered
+            res.refine_iterations_done = pipe.gesTrainCams(pipe.refine_cams == "all" ? reader.train_vec : pipe.refineKeyframeCams(),
+                                                           pipe.refine_iterations);
+            res.refine_log = pipe.refine_log;
+        }
         if (pipe.save_after_train) {
             for (const std::string& f : pipe.save(model, reader.train_vec)) res.files.push_back(f);
             pipe.saveEngine();

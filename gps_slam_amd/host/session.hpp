@@ -41,6 +41,9 @@ struct SessionResult {
     bool has_image_eval = false;
     int keyframe_count = 0;
     int gaussian_num = 0;
+    // PIPE.refine_iterations > 0: gesTrainCams between SLAMTrainCams and save -- the iterations it ran and its {iter, loss} log
+    int refine_iterations_done = 0;
+    std::vector<SLAMPipeline::RefineLogEntry> refine_log;
     SLAMPipeline::PipelineTimes times;
     std::vector<std::string> files;    // every file / directory the session wrote
 };
@@ -48,7 +51,9 @@ struct SessionResult {
 // The body of slam_trainer.cpp:26-75 on `reader`, which the caller has filled (loadConfig(root["READER"]) + train_vec).
 //   train / recon: model.loadConfig(MODEL); createWorkSpace(config_filename) if one is given (else workspace_dir is created, not
 //     emptied); pipe.loadConfig(PIPE, workspace_dir, true); SLAMTrainCams -- reader.train_vec[i].c2w_slam are the estimated poses
-//     afterwards; save_after_train: save, saveEngine, saveMesh, savePoses(eval_path + "/pose"); eval_after_train: the renders.
+//     afterwards; train with PIPE.refine_iterations > 0: gesTrainCams over refine_cams (keyframes: keyframe_cam_list + the live
+//     window; all: train_vec) for that many iterations; save_after_train: save, saveEngine, saveMesh, savePoses(eval_path + "/pose");
+//     eval_after_train: the renders.
 //   eval: model.loadConfig; loadParamsTensor(workspace_dir + "/gs_model/model.pt") (a workspace without one -- a recon run -- gives
 //     an empty model, and a line on stderr says so); pipe.loadConfig(PIPE, workspace_dir, false); loadEngine; the engine's
 //     per-frame poses and intrinsics (which its file does not hold) are restored from the reader's cameras: pose = c2w_slam, read from eval_path/pose/frame<id>.txt

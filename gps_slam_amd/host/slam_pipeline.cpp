@@ -103,12 +103,15 @@ torch::Tensor computeNormalMap(const torch::Tensor& vertex_map_in) {
 
 SLAMPipeline::SLAMPipeline(TsdfEngine* tsdf_engine, SLAMGaussianModel* model_, uint64_t seed, bool use_gt_pose)
     : main_engine(tsdf_engine), model(model_), rng_kf_(seed ^ 0x9E3779B97F4A7C15ull), rng_(seed), gen_(at::detail::createCPUGenerator(seed)) {
+    refine_seed = (int64_t)(seed & 0x7fffffffffffffffull);
     if (use_gt_pose) main_engine->turnOffTracking();
     device = model->device;
     voxel_size = main_engine->getVoxelSize();
 }
 
-SLAMPipeline::SLAMPipeline(uint64_t seed) : rng_kf_(seed ^ 0x9E3779B97F4A7C15ull), rng_(seed), gen_(at::detail::createCPUGenerator(seed)) {}
+SLAMPipeline::SLAMPipeline(uint64_t seed) : rng_kf_(seed ^ 0x9E3779B97F4A7C15ull), rng_(seed), gen_(at::detail::createCPUGenerator(seed)) {
+    refine_seed = (int64_t)(seed & 0x7fffffffffffffffull);
+}
 
 void SLAMPipeline::setTsdfEngine(InfiniTAM::Engine::CLIEngine* engine) {
     // an engine attached before must not call back into this pipeline (its Shutdown() would detach the new one)
@@ -189,6 +192,7 @@ void SLAMPipeline::applyConfig(const Config& c, bool from_node) {
     ConfigReader reader{c, from_node};
     configFields(reader);
     TORCH_CHECK(sample_method == "random" || sample_method == "ours", "sample_method: 'random' or 'ours', got '", sample_method, "'");
+    TORCH_CHECK(refine_cams == "keyframes" || refine_cams == "all", "refine_cams: 'keyframes' or 'all', got '", refine_cams, "'");
     if (log_iter == -1) log_iter = max_iterations - 1;   // src/pipeline.cpp:17-18
     updatePaths();
 }
@@ -429,7 +433,7 @@ SLAMPipeline::RaycastMs SLAMPipeline::buildViews(UpdateViews& out, const ViewSou
         }
         out.frame_id = src.frame_id;
         const int n = sample_method == "random" ? std::min<int>(keyframe_select_max, (int)src.keyframes.size()) : 0;   // :538
-        RandomSelector<Camera> sel(src.keyframes, rng_kf_);
+        ::RandomSelector<Camera> sel(src.keyframes, rng_kf_);
         for (int k = 0; k < n; k++) {
             const Camera* cam = sel.getNext().second;
             out.cams.push_back(*cam);
@@ -514,7 +518,7 @@ void SLAMPipeline::localOptimizeBegin() {
     opt_pending_ = 0;
     if (model->getGaussianNum() == 0) return;
     model->initOptimizers(-1, scene_scale);
-    opt_loader_.reset(new RandomSelector<Camera>(views_.cams, rng_));
+    opt_loader_.reset(new ::RandomSelector<Camera>(views_.cams, rng_));
     opt_peek_valid_ = false;
     opt_pending_ = local_opt_iters;
 }
@@ -526,35 +530,163 @@ void SLAMPipeline::optimizeIterations(int count) {
         // iteration's backward kernel could run its preprocessing forward in its tail (RawGaussianModel::trainStep next_cam)
         auto pick = opt_peek_valid_ ? opt_peek_ : opt_loader_->getNext();
         opt_peek_valid_ = false;
-        const Camera& cam = *pick.second;
-        TensorDict& rc = views_.raycasts[pick.first];
-        waitRaycast(views_.eventOf(pick.first));
         const Camera* next_cam = nullptr;
-        const bool terms = ssim_weight > 0 || depth_weight > 0;
-        // loss terms inside the fused step (fused_loss_terms), with or without an exposure row of the camera
-        const bool fused_terms = terms && fused_loss_terms;
-        if (prefetch_next_preprocess && opt_pending_ > 1 && (!terms || fused_terms)) {
+        if (canRunAhead() && opt_pending_ > 1) {
             opt_peek_ = opt_loader_->getNext();
             opt_peek_valid_ = true;
             next_cam = opt_peek_.second;
         }
-        Config wc;
-        if (terms) { wc.num["ssim_weight"] = ssim_weight; wc.num["depth_weight"] = depth_weight; }
-        if (fused_terms) {
-            model->trainStep(cam, rc.at("depth_map"), rc.at("color_map"), rc.at("depth_map_clamped"), next_cam, wc);
-        } else if (terms) {
-            // losses beyond L1: the reference's own sequence (slam_pipeline.cpp:247-254) through the autograd route
-            auto res = model->forward(cam, rc.at("depth_map"), rc.at("color_map"));
-            auto loss = model->computeLoss(res, cam, wc);
-            loss.at("total").backward();
-            model->optimizersStep();
-            model->optimizersZeroGrad();
-            autograd_iters++;
-        } else {
-            model->trainStep(cam, rc.at("depth_map"), rc.at("color_map"), rc.at("depth_map_clamped"), next_cam);
-        }
-        stats.opt_iters++;
+        optimizeOne(*pick.second, views_.raycasts[pick.first], views_.eventOf(pick.first), next_cam);
     }
+}
+
+void SLAMPipeline::optimizeOne(const Camera& cam, TensorDict& rc, RaycastEvent ev, const Camera* next_cam) {
+    waitRaycast(ev);
+    const bool terms = ssim_weight > 0 || depth_weight > 0;
+    // loss terms inside the fused step (fused_loss_terms), with or without an exposure row of the camera
+    const bool fused_terms = terms && fused_loss_terms;
+    Config wc;
+    if (terms) { wc.num["ssim_weight"] = ssim_weight; wc.num["depth_weight"] = depth_weight; }
+    if (fused_terms) {
+        model->trainStep(cam, rc.at("depth_map"), rc.at("color_map"), rc.at("depth_map_clamped"), next_cam, wc);
+    } else if (terms) {
+        // losses beyond L1: the reference's own sequence (slam_pipeline.cpp:247-254) through the autograd route
+        auto res = model->forward(cam, rc.at("depth_map"), rc.at("color_map"));
+        auto loss = model->computeLoss(res, cam, wc);
+        loss.at("total").backward();
+        model->optimizersStep();
+        model->optimizersZeroGrad();
+        autograd_iters++;
+    } else {
+        model->trainStep(cam, rc.at("depth_map"), rc.at("color_map"), rc.at("depth_map_clamped"), next_cam);
+    }
+    stats.opt_iters++;
+}
+
+// ------------------------------------------------------------------ gesTrainCams (src/pipeline.cpp:229-319)
+std::vector<Camera> SLAMPipeline::refineKeyframeCams() const {
+    std::vector<Camera> out(keyframe_cam_list);
+    for (const Camera& w : localframe_cam_window) {
+        bool have = false;
+        for (const Camera& k : out) have = have || k.id == w.id;
+        if (!have) out.push_back(w);
+    }
+    return out;
+}
+
+int64_t SLAMPipeline::refineCacheBytes(const std::vector<Camera>& cams) const {
+    int64_t bytes = 0;   // per pixel: colour 3 + depth 1 + clamped depth 1 floats of the base layers, 3 (+ 1 with a depth) of the camera's images
+    for (const Camera& cam : cams) bytes += (int64_t)cam.width * cam.height * (3 + 1 + 1 + 3 + (cam.depth.defined() ? 1 : 0)) * (int64_t)sizeof(float);
+    return bytes;
+}
+
+// cameras as the optimise iterations want them: copies whose image and pose pack are on the device
+static std::vector<Camera> refineDeviceCams(const std::vector<Camera>& cams, const torch::Device& device) {
+    std::vector<Camera> out(cams);
+    for (Camera& c : out) {
+        TORCH_CHECK(c.image.defined(), "gesTrainCams: camera ", c.id, " has no image");
+        c.toGPU(device);   // (a camera of the pipeline's lists is there already and keeps its upload)
+    }
+    return out;
+}
+
+int SLAMPipeline::gesTrainCams(const std::vector<Camera>& cams, int max_iters, int64_t seed) {
+    flush();
+    requireEngine("gesTrainCams");
+    TORCH_CHECK(!cams.empty(), "gesTrainCams: no cameras");
+    const int64_t need = refineCacheBytes(cams);
+    TORCH_CHECK(need <= refine_cache_mb * (int64_t(1) << 20), "gesTrainCams: the base layers and images of ", cams.size(), " cameras need ",
+                (need + (1 << 20) - 1) >> 20, " MiB on the device, refine_cache_mb allows ", refine_cache_mb,
+                " (fewer cameras -- refine_cams: keyframes -- or a larger refine_cache_mb)");
+    std::vector<Camera> dev = refineDeviceCams(cams, device);
+    // the base layers from the engine's final volume: runRaycastByCam(cam, false)'s maps, a batch of views at a time (the vertex and
+    // confidence maps of a batch are released before the next one)
+    std::vector<TensorDict> layers;
+    {
+        torch::NoGradGuard no_grad;
+        constexpr size_t kBatch = 12;
+        for (size_t base = 0; base < dev.size(); base += kBatch) {
+            std::vector<const Camera*> batch;
+            for (size_t k = base; k < std::min(dev.size(), base + kBatch); k++) batch.push_back(&dev[k]);
+            for (TensorDict& m : raycastCams(batch, main_engine->camPoses)) {
+                TensorDict keep;
+                for (const char* name : {"color_map", "depth_map", "depth_map_clamped"}) keep[name] = m.at(name);
+                layers.push_back(std::move(keep));
+            }
+        }
+    }
+    return refineLoop(dev, layers, max_iters, seed);
+}
+
+int SLAMPipeline::gesTrainCams(const std::vector<Camera>& cams, const std::vector<TensorDict>& base_layers, int max_iters, int64_t seed) {
+    flush();
+    TORCH_CHECK(!cams.empty(), "gesTrainCams: no cameras");
+    TORCH_CHECK(base_layers.size() == cams.size(), "gesTrainCams: ", base_layers.size(), " base layers for ", cams.size(), " cameras");
+    const int64_t need = refineCacheBytes(cams);
+    TORCH_CHECK(need <= refine_cache_mb * (int64_t(1) << 20), "gesTrainCams: the base layers and images of ", cams.size(), " cameras need ",
+                (need + (1 << 20) - 1) >> 20, " MiB on the device, refine_cache_mb allows ", refine_cache_mb,
+                " (fewer cameras -- refine_cams: keyframes -- or a larger refine_cache_mb)");
+    std::vector<Camera> dev = refineDeviceCams(cams, device);
+    std::vector<TensorDict> layers;
+    for (size_t k = 0; k < cams.size(); k++) {
+        TensorDict keep;
+        for (const auto& layer : {std::make_pair("color_map", 3), std::make_pair("depth_map", 1)}) {
+            const char* name = layer.first;
+            TORCH_CHECK(base_layers[k].count(name), "gesTrainCams: base layer ", k, " has no ", name);
+            keep[name] = base_layers[k].at(name).to(device, torch::kFloat32).contiguous();
+            TORCH_CHECK(keep[name].numel() == (int64_t)dev[k].width * dev[k].height * layer.second, "gesTrainCams: base layer ", k, ": ", name,
+                        " does not have the camera's image size");
+        }
+        keep["depth_map_clamped"] = RawGaussianModel::clampRefDepth(keep["depth_map"]);
+        layers.push_back(std::move(keep));
+    }
+    return refineLoop(dev, layers, max_iters, seed);
+}
+
+int SLAMPipeline::refineLoop(const std::vector<Camera>& cams, std::vector<TensorDict>& layers, int max_iters, int64_t seed) {
+    TORCH_CHECK(model != nullptr, "gesTrainCams: no model (SLAMTrainCams / setModel first)");
+    TORCH_CHECK(model->getRenderMethod() == "ges", "gesTrainCams: render_method must be 'ges', got '", model->getRenderMethod(), "'");   // :231
+    if (max_iters < 0) max_iters = max_iterations;
+    if (seed < 0) seed = refine_seed;
+    TORCH_CHECK(selected_cam_idx >= -1 && selected_cam_idx < (int)cams.size(), "gesTrainCams: selected_cam_idx ", selected_cam_idx, " with ",
+                cams.size(), " cameras");
+    if (curr_iter >= max_iters || model->getGaussianNum() == 0) return 0;
+    model->initOptimizers(refine_lr_decay ? max_iters : -1, scene_scale);   // ONE optimiser state for the whole call (:267)
+    gpsh::RandomSelector<Camera> loader(cams, (uint64_t)seed);
+    auto draw = [&]() -> size_t { return selected_cam_idx == -1 ? loader.getNext().originalIndex : (size_t)selected_cam_idx; };
+    // the L1 route accumulates its loss in lossSum(): each log entry is the mean since the last one (with loss weights lossSum() holds
+    // the last step's total and that is the entry)
+    const bool terms = ssim_weight > 0 || depth_weight > 0;
+    auto zeroLoss = [&] { if (model->lossSum().defined()) model->lossSum().zero_(); };
+    zeroLoss();
+    int since_log = 0;
+    const int first = curr_iter;
+    size_t next_idx = 0;
+    bool have_next = false;
+    for (; curr_iter < max_iters; curr_iter++) {
+        const size_t idx = have_next ? next_idx : draw();
+        have_next = false;
+        const Camera* next_cam = nullptr;
+        if (canRunAhead() && curr_iter + 1 < max_iters) {   // the next iteration's camera, one iteration early: the same draws in the same order
+            next_idx = draw();
+            have_next = true;
+            next_cam = &cams[next_idx];
+        }
+        model->updateSH(curr_iter);   // (a step whose successor has another degree arms nothing the successor accepts: PrefetchKey)
+        optimizeOne(cams[idx], layers[idx], nullptr, next_cam);
+        model->schedulersStep();
+        since_log++;
+        const bool last = curr_iter + 1 == max_iters;
+        if (last || (log_iter > 0 && (curr_iter + 1) % log_iter == 0)) {
+            torch::Tensor sum = model->lossSum();
+            const float value = sum.defined() ? sum.item<float>() : 0.f;   // (blocks: the loop's host synchronisation, with the check below)
+            refine_log.push_back({curr_iter, terms ? value : value / (float)since_log});
+            zeroLoss();
+            since_log = 0;
+            model->checkBinningCapacity();
+        }
+    }
+    return curr_iter - first;
 }
 
 // ------------------------------------------------------------------ removeRedundantGs :564-586

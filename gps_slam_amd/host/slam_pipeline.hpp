@@ -120,6 +120,34 @@ public:
     // empty model throw.
     ImageEvalResult evalImages(const std::vector<Camera>& cams, bool depth_mask = false, const std::string& source = "rgb");
 
+    // Pipeline::gesTrainCams (src/pipeline.cpp:229-319): the pass over ALL of `cams` once the sequence is over -- ONE
+    // initOptimizers(max_iterations, scene_scale) whose state lives for the whole call, the means' rate decaying to 0.01 x its
+    // start, the SH degree growing by MODEL.sh_degree_interval.  Per iteration: the camera from a gpsh::RandomSelector seeded with
+    // `seed` (or cams[selected_cam_idx]), drawn one iteration early so that the step can run the next camera's preprocessing
+    // ahead; updateSH(curr_iter); the iteration body of localOptimize (optimizeOne: same routes for exposure rows and loss
+    // weights); schedulersStep().  No prune, no new Gaussians.  flush() first; the engine's volume is read, never modified.
+    // Base layers: the reference reads pre-rendered mesh images (mesh_rgb_path / mesh_depth_path); here each camera's come from
+    // the attached engine's FINAL volume -- runRaycastByCam(cam, false)'s maps, batched, kept on the device (colour, depth,
+    // clamped depth) -- or, second overload, from the caller as one {"depth_map", "color_map"} pair per camera (the reference's
+    // file route; reading files stays outside).  If those layers plus the cameras' device images exceed refine_cache_mb the call
+    // throws before anything is allocated.  curr_iter is a member, as in the reference: a second call continues (and returns at
+    // once when curr_iter >= max_iterations).  Every log_iter iterations and at the last one lossSum() is read into refine_log
+    // and checkBinningCapacity() runs: the loop's only host synchronisations.  max_iterations < 0: this->max_iterations;
+    // seed < 0: refine_seed.  Returns the number of iterations run.
+    int gesTrainCams(const std::vector<Camera>& cams, int max_iterations = -1, int64_t seed = -1);
+    int gesTrainCams(const std::vector<Camera>& cams, const std::vector<TensorDict>& base_layers, int max_iterations = -1, int64_t seed = -1);
+    int64_t refineCacheBytes(const std::vector<Camera>& cams) const;   // what gesTrainCams holds on the device for these cameras
+    int curr_iter = 0;
+    struct RefineLogEntry { int iter; float loss; };
+    std::vector<RefineLogEntry> refine_log;
+    // PIPE keys of this project (all optional): what runSession does between SLAMTrainCams and save
+    int refine_iterations = 0;               // 0: no refinement
+    std::string refine_cams = "keyframes";   // "keyframes": keyframe_cam_list + the live window; "all": every train camera
+    int64_t refine_seed = 1234;              // (the constructor's seed unless the key is given)
+    int64_t refine_cache_mb = 16384;
+    bool refine_lr_decay = true;             // (no key) false: gesTrainCams builds its optimisers without the scheduler -- constant rates
+    std::vector<Camera> refineKeyframeCams() const;   // the "keyframes" set (a window camera that is a keyframe too counts once)
+
     // slam_pipeline.h:32-49: mesh / engine state files under workspace_dir (empty names are skipped like the reference)
     std::string workspace_dir = ".", saved_mesh, saved_engine;
     void saveMesh() { if (!saved_mesh.empty()) main_engine->SaveSceneToMesh((workspace_dir + "/" + saved_mesh).c_str()); }
@@ -134,8 +162,8 @@ public:
     AteResult evalTrajectory();
 
     // Pipeline::loadConfig's session settings (src/pipeline.cpp:9-22).  The *_cfg strings are the file's ("/gs_model", "/log", "/val");
-    // model_path / log_path / eval_path = workspace_dir + them.  max_iterations, selected_cam_idx, log_iter, log_slam_state and
-    // enable_densify are stored only: the SLAM loop uses none of them.
+    // model_path / log_path / eval_path = workspace_dir + them.  max_iterations, selected_cam_idx and log_iter are gesTrainCams';
+    // log_slam_state and enable_densify are stored only.
     bool eval_after_train = false, save_after_train = false, enable_densify = false, log_slam_state = false;
     int max_iterations = 10000, selected_cam_idx = -1, log_iter = 1000;
     std::string model_path_cfg = "/gs_model", log_path_cfg = "/log", eval_path_cfg = "/val";
@@ -356,6 +384,16 @@ private:
     std::atomic<double> job_post_ms_{0.0};        // (debug aid only: when the frame thread woke the mapping thread)
     void localOptimizeBegin();
     void optimizeIterations(int count);
+    // One optimise iteration on `cam` over its base layers `rc` (depth_map, color_map, depth_map_clamped; ev: the event behind
+    // them or nullptr): the fused trainStep, with the loss weights inside it (fused_loss_terms), or the reference's sequence
+    // through autograd.  THE iteration body of localOptimize and of gesTrainCams.  next_cam: see RawGaussianModel::trainStep;
+    // pass one only where canRunAhead().
+    void optimizeOne(const Camera& cam, TensorDict& rc, RaycastEvent ev, const Camera* next_cam);
+    int refineLoop(const std::vector<Camera>& cams, std::vector<TensorDict>& layers, int max_iterations, int64_t seed);   // gesTrainCams behind its base layers
+    bool canRunAhead() const {
+        const bool terms = ssim_weight > 0 || depth_weight > 0;
+        return prefetch_next_preprocess && (!terms || fused_loss_terms);
+    }
     void pumpMapping(int count);
     std::unique_ptr<RandomSelector<Camera>> opt_loader_;
     std::pair<int, const Camera*> opt_peek_{0, nullptr};   // the next iteration's camera, drawn one iteration early (optimizeIterations)
@@ -437,6 +475,10 @@ void SLAMPipeline::configFields(V& v) {
     // (The flat route does accept the session keys above -- model_path, eval_after_train, saved_mesh ... -- which it had no field
     // for before.)
     v.b("fused_loss_terms", fused_loss_terms, gpsh::kOptional);
+    v.i("refine_iterations", refine_iterations, gpsh::kOptional);
+    v.s("refine_cams", refine_cams, gpsh::kOptional);
+    v.i64("refine_seed", refine_seed, gpsh::kOptional);
+    v.i64("refine_cache_mb", refine_cache_mb, gpsh::kOptional);
     v.b("overlap_mapping", overlap_mapping, gpsh::kNodeOnly);
     v.b("mapping_thread", mapping_thread, gpsh::kNodeOnly);
     v.b("async_raycasts", async_raycasts, gpsh::kNodeOnly);
@@ -454,6 +496,11 @@ gpsh::Config SLAMPipeline::flattenConfig(const N& pipe_node) {
     gpsh::Config flat = gpsh::flattenNode(pipe_node, "PIPE", [&](auto& v) { configFields(v); });
     if (flat.get("enable_densify", 0.0) != 0.0)
         throw gpsh::ConfigError(gpsh::nodePath(pipe_node, "PIPE") + ".enable_densify: densification is not supported (set it to false)");
+    const std::string which = flat.gets("refine_cams", "keyframes");
+    if (which != "keyframes" && which != "all")
+        throw gpsh::ConfigError(gpsh::nodePath(pipe_node, "PIPE") + ".refine_cams: 'keyframes' or 'all', got '" + which + "'");
+    if (flat.get("refine_iterations", 0.0) < 0.0)
+        throw gpsh::ConfigError(gpsh::nodePath(pipe_node, "PIPE") + ".refine_iterations: must not be negative");
     return flat;
 }
 

@@ -19,6 +19,7 @@ import torch
 
 from ._lib import check, lib
 from .gs_model import Camera, SLAMGaussianModel, pose_inv  # noqa: F401
+from . import random_selector
 
 DEFAULT_PIPE = dict(new_gs_sample_ratio=0.25, color_error_thres=0.05, localframe_cam_window_length=2,
                     localframe_cam_window_interval=5, local_opt_iters=20, local_opt_interval=10,
@@ -79,6 +80,12 @@ class SLAMPipeline:
         self.stats = dict(frames=0, opt_iters=0, raycasts=0, added=0, pruned=0)
         self.workspace_dir, self.saved_mesh, self.saved_engine = ".", "", ""
         self.gtC2wPoses = []  # dataset pose of every processed frame (ITMBasicEngine::gtC2wPoses), for evalTrajectory
+        # Pipeline::loadConfig's session settings gesTrainCams reads (src/pipeline.cpp:9-22) and this project's refine_* keys
+        self.max_iterations, self.selected_cam_idx, self.log_iter = 10000, -1, 1000
+        self.refine_iterations, self.refine_cams, self.refine_seed, self.refine_cache_mb = 0, "keyframes", seed, 16384
+        self.refine_lr_decay = True   # False: gesTrainCams builds its optimisers without the scheduler (constant rates)
+        self.curr_iter = 0
+        self.refine_log = []   # (iter, loss) every log_iter iterations of gesTrainCams and at the last one
 
     @classmethod
     def from_config(cls, nested, tsdf_engine, model, seed=1234):
@@ -96,6 +103,13 @@ class SLAMPipeline:
         pipe = cls(tsdf_engine, model, pipe_cfg, seed=seed, work_mode=nested["work_mode"].as_str(), use_gt_pose=flat["use_gt_pose"])
         pipe.workspace_dir = nested["workspace_dir"].as_str()
         pipe.saved_mesh, pipe.saved_engine = flat["saved_mesh"], flat["saved_engine"]
+        pipe.max_iterations, pipe.selected_cam_idx, pipe.log_iter = flat["max_iterations"], flat["selected_cam_idx"], flat["log_iter"]
+        if pipe.log_iter == -1:
+            pipe.log_iter = pipe.max_iterations - 1   # src/pipeline.cpp:17-18
+        refine = config.refine_settings(nested["PIPE"])
+        pipe.refine_iterations, pipe.refine_cams, pipe.refine_cache_mb = refine["refine_iterations"], refine["refine_cams"], refine["refine_cache_mb"]
+        if refine["refine_seed"] is not None:
+            pipe.refine_seed = refine["refine_seed"]
         return pipe
 
     # ------------------------------------------------------------------ slam_pipeline.h:32-49
@@ -217,10 +231,81 @@ class SLAMPipeline:
         loader = RandomSelector(self.opt_cam_list, self.rng)
         for _ in range(self.cfg["local_opt_iters"]):
             idx, cam = loader.getNext()
-            rc = self.opt_raycast_list[idx]
-            model.train_step(cam, rc["depth_map"], rc["color_map"], cam.image,
-                             ref_depth_clamped=rc["depth_map_clamped"])
-            self.stats["opt_iters"] += 1
+            self._optimize_one(cam, self.opt_raycast_list[idx])
+
+    def _optimize_one(self, cam, rc, next_cam=None):
+        """one optimise iteration on `cam` over its base layers: THE iteration body of localOptimize and of gesTrainCams"""
+        self.model.train_step(cam, rc["depth_map"], rc["color_map"], cam.image, ref_depth_clamped=rc["depth_map_clamped"],
+                              next_cam=next_cam)
+        self.stats["opt_iters"] += 1
+
+    # ------------------------------------------------------------------ gesTrainCams (src/pipeline.cpp:229-319)
+    def refineKeyframeCams(self):
+        """the "keyframes" set of refine_cams: keyframe_cam_list plus the live window (a camera in both counts once)"""
+        out = list(self.keyframe_cam_list)
+        out += [w for w in self.localframe_cam_window if all(k.id != w.id for k in out)]
+        return out
+
+    @staticmethod
+    def refineCacheBytes(cams):
+        """per pixel: colour 3 + depth 1 + clamped depth 1 floats of the base layers, 3 (+ 1 with a depth) of the camera's images"""
+        return sum(c.width * c.height * (3 + 1 + 1 + 3 + (1 if c.depth is not None else 0)) * 4 for c in cams)
+
+    def gesTrainCams(self, cams, max_iterations=-1, seed=-1, base_layers=None):
+        """Mirror of SLAMPipeline::gesTrainCams (host/slam_pipeline.hpp): the pass over all of `cams` once the sequence is over,
+        with ONE optimiser state, the means' rate decaying to 0.01 x its start and the SH degree growing by sh_degree_interval.
+        Base layers: each camera's free view of the engine's final volume, or `base_layers` (one dict with depth_map and
+        color_map per camera).  -> the number of iterations run."""
+        model = self.model
+        if not cams:
+            raise ValueError("gesTrainCams: no cameras")
+        need = self.refineCacheBytes(cams)
+        if need > self.refine_cache_mb << 20:
+            raise RuntimeError("gesTrainCams: the base layers and images of %d cameras need %d MiB on the device, refine_cache_mb allows %d"
+                               % (len(cams), (need + (1 << 20) - 1) >> 20, self.refine_cache_mb))
+        for cam in cams:
+            cam.toGPU()
+        if base_layers is None:
+            layers = []
+            for cam in cams:
+                m = self.runRaycastByCam(cam)
+                layers.append({k: m[k] for k in ("color_map", "depth_map", "depth_map_clamped")})
+        else:
+            if len(base_layers) != len(cams):
+                raise ValueError("gesTrainCams: %d base layers for %d cameras" % (len(base_layers), len(cams)))
+            layers = [dict(color_map=b["color_map"].to(self.device, torch.float32).contiguous(),
+                           depth_map=b["depth_map"].to(self.device, torch.float32).contiguous()) for b in base_layers]
+            for b in layers:
+                b["depth_map_clamped"] = model.clamp_ref_depth(b["depth_map"])
+        if max_iterations < 0:
+            max_iterations = self.max_iterations
+        if seed < 0:
+            seed = self.refine_seed
+        if not -1 <= self.selected_cam_idx < len(cams):
+            raise ValueError("gesTrainCams: selected_cam_idx %d with %d cameras" % (self.selected_cam_idx, len(cams)))
+        if self.curr_iter >= max_iterations or model.getGaussianNum() == 0:
+            return 0
+        model.initOptimizers(max_iterations if self.refine_lr_decay else -1, self.cfg["scene_scale"])
+        loader = random_selector.RandomSelector(cams, seed)
+        draw = (lambda: loader.getNext()[1]) if self.selected_cam_idx == -1 else (lambda: self.selected_cam_idx)
+        if model._B is not None:
+            model.loss_sum().zero_()
+        first, since_log, nxt = self.curr_iter, 0, None
+        while self.curr_iter < max_iterations:
+            idx = draw() if nxt is None else nxt
+            nxt = draw() if self.curr_iter + 1 < max_iterations else None   # one iteration early: the same draws in the same order
+            model.updateSH(self.curr_iter)
+            self._optimize_one(cams[idx], layers[idx], None if nxt is None else cams[nxt])
+            model.schedulersStep()
+            since_log += 1
+            last = self.curr_iter + 1 == max_iterations
+            if last or (self.log_iter > 0 and (self.curr_iter + 1) % self.log_iter == 0):
+                self.refine_log.append((self.curr_iter, float(model.loss_sum()) / since_log))
+                model.loss_sum().zero_()
+                since_log = 0
+                model.check_binning_capacity()
+            self.curr_iter += 1
+        return self.curr_iter - first
 
     # ------------------------------------------------------------------ removeRedundantGs :564-586
     def removeRedundantGs(self):
