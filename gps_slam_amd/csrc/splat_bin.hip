@@ -30,25 +30,6 @@ constexpr int SORT_ITEMS = 8;           // items per thread
 constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;  // 2048 items per workgroup
 constexpr int SCAN_THREADS = 1024;
 
-// ---- workgroup-wide exclusive scan of one int per thread (blockDim multiple of 64, <= 1024) ----
-__device__ __forceinline__ int block_excl_scan(int v, int* lds_wave_sums /*[17]*/, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    int incl = wave_incl_scan_i(v);
-    if (lane == 63) lds_wave_sums[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        int s = lane < nwaves ? lds_wave_sums[lane] : 0;
-        int si = wave_incl_scan_i(s);
-        if (lane < nwaves) lds_wave_sums[lane] = si - s;
-        if (lane == 63) lds_wave_sums[16] = si;
-    }
-    __syncthreads();
-    int r = lds_wave_sums[wave] + incl - v;
-    total = lds_wave_sums[16];
-    __syncthreads();
-    return r;
-}
-
 // ---------------- pass 1: per-Gaussian counts + per-block sums ----------------
 __global__ __launch_bounds__(BIN_BLOCK) void count_kernel(int N, const float* __restrict__ means2d,
                                                          const int32_t* __restrict__ radii, int tile_size, int tw,
@@ -87,24 +68,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_blocks_kernel(int nblk, int
                                                                   int64_t isect_cap, int64_t group_cap,
                                                                   int64_t* __restrict__ counts) {
     __shared__ int ws[17];
-    const int per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int lo = threadIdx.x * per, hi = min(nblk, lo + per);
-    int totals[2];
-    for (int which = 0; which < 2; which++) {
-        int32_t* a = which == 0 ? blk_tiles : blk_groups;
-        int s = 0;
-        for (int k = lo; k < hi; k++) s += a[k];
-        int total;
-        int base = block_excl_scan(s, ws, total);
-        for (int k = lo; k < hi; k++) { int v = a[k]; a[k] = base; base += v; }
-        totals[which] = total;
-    }
+    const int n_tiles = block_scan_counts<SCAN_THREADS>(blk_tiles, nblk, ws);
+    const int n_groups = block_scan_counts<SCAN_THREADS>(blk_groups, nblk, ws);
     int s = 0;
-    for (int k = lo; k < hi; k++) s += blk_vis[k];
+    for (int k = threadIdx.x; k < nblk; k += SCAN_THREADS) s += blk_vis[k];
     int vis_total;
-    block_excl_scan(s, ws, vis_total);
+    block_excl_scan<SCAN_THREADS>(s, ws, vis_total);
     if (threadIdx.x == 0) {
-        int64_t ni = totals[0], ng = totals[1];
+        int64_t ni = n_tiles, ng = n_groups;
         int64_t ovf = 0;
         if (ni > isect_cap) { ni = isect_cap; ovf = 1; }
         if (ng > group_cap) { ng = group_cap; ovf = 1; }
@@ -150,17 +121,17 @@ __global__ __launch_bounds__(BIN_BLOCK) void expand_kernel(int N, const float* _
         }
     }
     int tot_t, tot_g;
-    int et = block_excl_scan(t, ws, tot_t);
-    int eg = block_excl_scan(g, ws, tot_g);
+    int et = block_excl_scan<BIN_BLOCK>(t, ws, tot_t);
+    int eg = block_excl_scan<BIN_BLOCK>(g, ws, tot_g);
     pre_t[tid] = et; pre_g[tid] = eg;
     if (tid == 0) { pre_t[BIN_BLOCK] = tot_t; pre_g[BIN_BLOCK] = tot_g; }
     __syncthreads();
     int pt = 0, pg = 0, pv = 0;
     for (int k = tid; k < (int)blockIdx.x; k += BIN_BLOCK) { pt += blk_tiles[k]; pg += blk_groups[k]; pv += blk_vis[k]; }
     int sum_t, sum_g, sum_v;
-    block_excl_scan(pt, ws, sum_t);
-    block_excl_scan(pg, ws, sum_g);
-    block_excl_scan(pv, ws, sum_v);
+    block_excl_scan<BIN_BLOCK>(pt, ws, sum_t);
+    block_excl_scan<BIN_BLOCK>(pg, ws, sum_g);
+    block_excl_scan<BIN_BLOCK>(pv, ws, sum_v);
     const int64_t base_t = sum_t, base_g = sum_g;
     if (blockIdx.x == gridDim.x - 1 && tid == 0) {
         int64_t ni = base_t + tot_t, ng = base_g + tot_g;
@@ -223,13 +194,7 @@ __global__ __launch_bounds__(256) void radix_scan_kernel(const int64_t* __restri
     const int n = (int)counts[0];
     const int nblk = (n + SORT_TILE - 1) / SORT_TILE;
     uint32_t* row = hist + (size_t)blockIdx.x * nblk_cap;
-    const int per = (nblk + 255) / 256;
-    const int lo = min(nblk, (int)threadIdx.x * per), hi = min(nblk, lo + per);
-    int s = 0;
-    for (int b = lo; b < hi; b++) s += (int)row[b];
-    int tot;
-    int run = block_excl_scan(s, ws, tot);
-    for (int b = lo; b < hi; b++) { int v = (int)row[b]; row[b] = (uint32_t)run; run += v; }
+    const int tot = block_scan_counts<256>(reinterpret_cast<int32_t*>(row), nblk, ws);   // (counts below 2^31)
     if (threadIdx.x == 0) digit_total[blockIdx.x] = (uint32_t)tot;
 }
 
@@ -279,7 +244,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(const uint3
     __shared__ int dws[17];
     int dtot;
     const int dval = (int)threadIdx.x < bins ? (int)digit_total[threadIdx.x] : 0;
-    const int dexcl = block_excl_scan(dval, dws, dtot);
+    const int dexcl = block_excl_scan<SORT_THREADS>(dval, dws, dtot);
     if ((int)threadIdx.x < bins) {
         uint32_t run = (uint32_t)dexcl + hist[(size_t)threadIdx.x * nblk_cap + blockIdx.x];
         digitbase[threadIdx.x] = run;
@@ -349,7 +314,7 @@ __global__ __launch_bounds__(SORT_THREADS) void wide_scatter_kernel(const uint32
     if (n > 0)
         for (int b = lo; b < hi; b++) sum += (int)digit_total[b];
     int dtot;
-    int run = block_excl_scan(sum, dws, dtot);
+    int run = block_excl_scan<SORT_THREADS>(sum, dws, dtot);
     for (int b = lo; b < hi; b++) {
         digitbase[b] = (uint32_t)run;
         if (blockIdx.x == 0) tile_offsets[b] = run;

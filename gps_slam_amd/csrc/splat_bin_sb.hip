@@ -36,11 +36,6 @@ __device__ __forceinline__ int wave_min_i(int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
     return v;
 }
-__device__ __forceinline__ int wave_excl_scan_i(int v, int& total) {
-    const int incl = wave_incl_scan_i(v);
-    total = __shfl(incl, 63, 64);
-    return incl - v;
-}
 
 // ---- one wave per tile: exclusive prefix of the tile's row of C over the superblocks; C is left zero ----
 __global__ __launch_bounds__(256) void sb_scan_kernel(int n_tiles, SbTables t, gps::LaunchStamp stamp) {

@@ -162,9 +162,7 @@ __global__ __launch_bounds__(CM_THREADS) void mask_write_kernel(int n, const uin
     uint32_t w[4];
     const int first = blockIdx.x * CM_BLOCK + threadIdx.x * CM_PER;
     const int c = load_mask16(n, mask, first, w);
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    const int incl = wave_incl_scan_i(c);
     if (lane == 63) ws[wave] = incl;
     __syncthreads();
     int run = ws[CM_THREADS / 64] + incl - c;

@@ -24,43 +24,56 @@ constexpr int BAND_STEP_BITS = 6;
 constexpr int MAX_BAND_STEPS = 1 << BAND_STEP_BITS;
 constexpr float FAR_AWAY = 999999.9f;
 constexpr float VERY_CLOSE = 0.05f;
-constexpr int MINMAX_SUB = 8;
+constexpr int MINMAX_SUB = 8;    // pixels per cell edge of the min/max (expected-depth) image
+constexpr int SWEEP_SLOTS = 1024;  // hash slots per workgroup of the ordered sweeps (allocation, visible lists, mesh entries)
 constexpr int MAX_RENDERING_BLOCKS = 65536 * 4;
 constexpr int ED_GROUPS = 128;  // per-workgroup partial min/max images of CreateExpectedDepths (x 512 threads: one visible block per thread up to 65,536)
 
-// Layout of gps_tsdf_state.scan_scratch (int32 words; sized by gps_tsdf_scratch_bytes):
-//   [3 * nblk + 16]             per-1024-slot counts of the ordered sweeps + totals
-//   [(n_total + 3) / 4 + 2]     one flag byte per hash slot (visible-list compaction)
-//   [ED_GROUPS * sw * sh * 2]   partial min/max images
-//   [16]                        pad
-//   [n_buckets / 32]            PERSISTENT: one bit per bucket, set iff its head entry is non-empty (ptr != -2).  Blocks are
-//                               never freed, so alloc_apply only ever sets bits; gps_tsdf_reset clears them,
+__host__ __device__ __forceinline__ int sweep_blocks(const gps_tsdf_state& s) { return (s.n_buckets + s.n_excess + SWEEP_SLOTS - 1) / SWEEP_SLOTS; }
+__host__ __device__ inline int ray_stat_waves(const gps_tsdf_state& s) { return ((s.width + 7) / 8) * ((s.height + 7) / 8) * 4; }  // (room for 4 x 4 pixel waves)
+
+// Layout of gps_tsdf_state.scan_scratch, THE one description of it: offsets in int32 words from the start of the buffer, in this
+// order (nblk = sweep_blocks, n_total = n_buckets + n_excess, sw x sh = (width / MINMAX_SUB + 2) x (height / MINMAX_SUB + 2)):
+//   counts[0..2]  [nblk] each     per-SWEEP_SLOTS-slot counts of the ordered sweeps: type-1 requests, type-2 requests, visible slots
+//   totals        [16]            sums of the two request counts (scratch of the allocation's scan)
+//   flags         [(n_total + 3) / 4 + 2]   one flag BYTE per hash slot (visible-list compaction)
+//   partials      [ED_GROUPS * sw * sh * 2] partial min/max images, then [16] pad
+//   bucket_bits   [n_buckets / 32]          PERSISTENT: one bit per bucket, set iff its head entry is non-empty (ptr != -2).
+//                               Blocks are never freed, so alloc_apply only ever sets bits; gps_tsdf_reset clears them,
 //                               gps_tsdf_rebuild_index recomputes them from the table (after a scene was loaded into it).
 //                               The raycaster's free-space march asks this 128 KB bitmap instead of the 16 MB table.
-//   [16]                        pad
-//   [4 + 4 * waves]             ray statistics of the last raycast launch (ray_stats_rows below), waves = 4 per 16 x 16 pixel patch
-static inline int64_t scratch_words_before_bits(const gps_tsdf_state& s) {
+//                               Then [16] pad.
+//   ray_stats     [4 * ray_stat_waves]      rows of the LAST raycast launch on this scratch, 16-byte aligned: one {castRay steps,
+//                               voxel reads, rays, longest ray} quadruple of floats per wave of that launch, written with plain
+//                               stores (no atomics, no zero-fill; gps_tsdf_ray_stats sums them into
+//                               counters[GPS_TSDF_RAY_STEPS..] on demand)
+//   total         what gps_tsdf_scratch_bytes reports, in words (4 words of slack for the alignment of the rows)
+// The scratch of a free view (gps_tsdf_view.scratch) has the same layout; only counts[2], flags and partials of it are used.
+struct ScratchLayout { int64_t counts[3], totals, flags, partials, bucket_bits, ray_stats, total; };
+__host__ __device__ inline ScratchLayout scratch_layout(const gps_tsdf_state& s) {
     const int64_t n_total = (int64_t)s.n_buckets + s.n_excess;
-    const int64_t nblk = (n_total + 1023) / 1024;
+    const int64_t nblk = (n_total + SWEEP_SLOTS - 1) / SWEEP_SLOTS;
     const int64_t sw = s.width / MINMAX_SUB + 2, sh = s.height / MINMAX_SUB + 2;
-    return 3 * nblk + 16 + (n_total + 3) / 4 + 2 + (int64_t)ED_GROUPS * sw * sh * 2 + 16;
+    ScratchLayout l;
+    l.counts[0] = 0; l.counts[1] = nblk; l.counts[2] = 2 * nblk;
+    l.totals = 3 * nblk;
+    l.flags = l.totals + 16;
+    l.partials = l.flags + (n_total + 3) / 4 + 2;
+    l.bucket_bits = l.partials + (int64_t)ED_GROUPS * sw * sh * 2 + 16;
+    const int64_t behind_bits = l.bucket_bits + ((int64_t)s.n_buckets + 31) / 32 + 16;
+    l.ray_stats = (behind_bits + 3) & ~(int64_t)3;
+    l.total = behind_bits + 4 + 4 * (int64_t)ray_stat_waves(s);
+    return l;
 }
-static inline uint32_t* bucket_bits(const gps_tsdf_state& s) {
-    return reinterpret_cast<uint32_t*>(s.scan_scratch) + scratch_words_before_bits(s);
-}
-// behind the bitmap (+ 16 words of pad): the ray statistics of the LAST raycast launch on this scratch, one {castRay steps,
-// voxel reads, rays, 0} quadruple of floats per wave of that launch, written with plain stores (no atomics, no zero-fill;
-// gps_tsdf_ray_stats sums them into counters[GPS_TSDF_RAY_STEPS..] on demand)
-__host__ __device__ inline int ray_stat_waves(const gps_tsdf_state& s) { return ((s.width + 7) / 8) * ((s.height + 7) / 8) * 4; }  // (room for 4 x 4 pixel waves)
-__host__ __device__ inline int64_t ray_stats_offset_words(const gps_tsdf_state& s) {
-    const int64_t n_total = (int64_t)s.n_buckets + s.n_excess;
-    const int64_t nblk = (n_total + 1023) / 1024;
-    const int64_t sw = s.width / 8 + 2, sh = s.height / 8 + 2;
-    return 3 * nblk + 16 + (n_total + 3) / 4 + 2 + (int64_t)ED_GROUPS * sw * sh * 2 + 16 + ((int64_t)s.n_buckets + 31) / 32 + 16;
-}
-__host__ __device__ inline float4* ray_stats_rows(const gps_tsdf_state& s) {
-    return reinterpret_cast<float4*>(s.scan_scratch + ((ray_stats_offset_words(s) + 3) & ~(int64_t)3));   // (16-byte aligned rows)
-}
+// the regions as pointers (counts and flags start below 2^31 words for every table whose slots an int can count: 32-bit offsets in
+// the sweep kernels)
+__host__ __device__ __forceinline__ int32_t* scratch_at(const gps_tsdf_state& s, int64_t word) { return s.scan_scratch + word; }
+__host__ __device__ __forceinline__ int32_t* sweep_counts(const gps_tsdf_state& s, int which) { return scratch_at(s, (int)scratch_layout(s).counts[which]); }
+__host__ __device__ __forceinline__ int32_t* sweep_totals(const gps_tsdf_state& s) { return scratch_at(s, scratch_layout(s).totals); }
+__host__ __device__ __forceinline__ uint8_t* sweep_flags(const gps_tsdf_state& s) { return reinterpret_cast<uint8_t*>(scratch_at(s, (int)scratch_layout(s).flags)); }
+__host__ __device__ __forceinline__ uint2* minmax_partials(const gps_tsdf_state& s) { return reinterpret_cast<uint2*>(scratch_at(s, scratch_layout(s).partials)); }
+__host__ __device__ __forceinline__ uint32_t* bucket_bits(const gps_tsdf_state& s) { return reinterpret_cast<uint32_t*>(scratch_at(s, scratch_layout(s).bucket_bits)); }
+__host__ __device__ __forceinline__ float4* ray_stats_rows(const gps_tsdf_state& s) { return reinterpret_cast<float4*>(scratch_at(s, scratch_layout(s).ray_stats)); }
 
 struct Mat4 { float m[16]; };  // ORUtils layout m[col*4 + row]
 
@@ -89,15 +102,6 @@ __device__ __forceinline__ void apply_view(TsdfState& s, const ViewRec& v) {
     s.fv_visible_ids = v.visible_ids; s.fv_minmax = v.minmax; s.fv_raycast = v.raycast; s.fv_colour = v.colour;
     s.scan_scratch = v.scratch; s.counters = v.counters;
     s.fx = v.fx; s.fy = v.fy; s.cx = v.cx; s.cy = v.cy;
-}
-// regions of scan_scratch the ordered visible-list sweep and the expected-depth pass use (see the layout above)
-__host__ __device__ __forceinline__ int sweep_blocks(const TsdfState& s) { return (s.n_buckets + s.n_excess + 1023) / 1024; }
-__host__ __device__ __forceinline__ int32_t* sweep_counts(const TsdfState& s) { return s.scan_scratch + 2 * sweep_blocks(s); }
-__host__ __device__ __forceinline__ uint8_t* sweep_flags(const TsdfState& s) {
-    return reinterpret_cast<uint8_t*>(s.scan_scratch + 3 * sweep_blocks(s) + 16);
-}
-__host__ __device__ __forceinline__ uint2* minmax_partials(const TsdfState& s) {
-    return reinterpret_cast<uint2*>(s.scan_scratch + 3 * sweep_blocks(s) + 16 + (s.n_buckets + s.n_excess + 3) / 4 + 2);
 }
 
 static inline bool state_valid(const gps_tsdf_state& s) {

@@ -165,11 +165,6 @@ __global__ __launch_bounds__(CAST_THREADS) void forward_cast_kernel(TsdfState s,
     }
 }
 
-inline double wall_ms() {
-    timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
-    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
-
 }  // namespace
 
 extern "C" {

@@ -21,7 +21,7 @@
 //  * Integration: one wave64 per visible block walking its 8 z-slices (coalesced 512-byte slice
 //    accesses, 8-byte voxel per lane), ~8k blocks in flight to hide the per-block header latency.
 #include "launch_timing.hpp"
-#include "tsdf_common.hpp"
+#include "tsdf_sweep.hpp"
 
 using namespace gpst;
 
@@ -161,54 +161,16 @@ __global__ __launch_bounds__(256) void alloc_request_kernel(TsdfState s, Mat4 in
 }
 
 // ---------------------------------------------------------------- ordered sweeps over the hash slots
-constexpr int SWEEP = 1024;  // slots per workgroup
 constexpr int SCAN_THREADS = 256;  // the single-workgroup scan of the per-workgroup counts (<= 1,152 of them: 5 per thread)
 
-__device__ __forceinline__ int block_excl_scan_1024(int v, int* ws /*[17]*/, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = wave_incl_scan_i(v);
-    if (lane == 63) ws[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        const int nw = (int)blockDim.x >> 6;  // (16 waves or fewer)
-        int sv = lane < nw ? ws[lane] : 0;
-        int si = wave_incl_scan_i(sv);
-        if (lane < nw) ws[lane] = si - sv;
-        if (lane == 63) ws[16] = si;
-    }
-    __syncthreads();
-    int r = ws[wave] + incl - v;
-    total = ws[16];
-    __syncthreads();
-    return r;
-}
-
-// The sweeps' workgroups: SWEEP slots each, walked by SWEEP_THREADS threads that own SLOTS_PER_THREAD CONSECUTIVE slots (so the
+// The sweeps' workgroups: SWEEP_SLOTS slots each, walked by SWEEP_THREADS threads that own SLOTS_PER_THREAD CONSECUTIVE slots (so the
 // order of a compaction is still the slot order).  Round 3: 256 threads x 4 slots instead of 1,024 x 1 -- a 16-wave workgroup
 // needs four free wave slots on every SIMD of ONE compute unit at the same moment, and beside the map stream's rasterizer
 // (8-wave workgroups that refill a unit as soon as one of them retires) it waited for that for up to 50 us (rocprof, overlap
 // table: alloc_count / alloc_apply / visible_count 13-16 us on average against 8 alone, max 48-52); a 4-wave workgroup fits into
 // the hole ANY retiring rasterizer workgroup leaves.
-constexpr int SWEEP_THREADS = 256, SLOTS_PER_THREAD = SWEEP / SWEEP_THREADS;
-static_assert(SLOTS_PER_THREAD == 4 && SWEEP_THREADS == 256, "block_excl_scan_4 is written for 4 waves x 4 slots");
-
-// exclusive prefix of v[0..3] of every thread over the workgroup's 1,024 slots (thread-major), total to `total`
-__device__ __forceinline__ void block_excl_scan_4(const int (&v)[4], int* ws /*[5]*/, int (&excl)[4], int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int mine = v[0] + v[1] + v[2] + v[3];
-    const int incl = wave_incl_scan_i(mine);
-    if (lane == 63) ws[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int a = ws[0], b = ws[1], c = ws[2], d = ws[3];
-        ws[0] = 0; ws[1] = a; ws[2] = a + b; ws[3] = a + b + c; ws[4] = a + b + c + d;
-    }
-    __syncthreads();
-    excl[0] = ws[wave] + incl - mine;
-    excl[1] = excl[0] + v[0]; excl[2] = excl[1] + v[1]; excl[3] = excl[2] + v[2];
-    total = ws[4];
-    __syncthreads();
-}
+constexpr int SWEEP_THREADS = 256, SLOTS_PER_THREAD = SWEEP_SLOTS / SWEEP_THREADS;
+static_assert(SLOTS_PER_THREAD == 4 && SWEEP_THREADS == 256, "block_excl_scan_4 (common.hpp) is written for 4 waves x 4 slots");
 
 // request type of a slot given the PRE-allocation table: empty bucket -> 1 (ordered), occupied chain end -> 2
 __device__ __forceinline__ int request_type(const TsdfState& s, int idx) {
@@ -219,7 +181,7 @@ __device__ __forceinline__ int request_type(const TsdfState& s, int idx) {
 __global__ __launch_bounds__(SWEEP_THREADS) void alloc_count_kernel(TsdfState s, int32_t* __restrict__ blk1, int32_t* __restrict__ blk2) {
     GPS_FRAME_PRIO();
     __shared__ int ws[5];
-    const int idx0 = blockIdx.x * SWEEP + threadIdx.x * SLOTS_PER_THREAD;
+    const int idx0 = blockIdx.x * SWEEP_SLOTS + threadIdx.x * SLOTS_PER_THREAD;
     const int n_total = s.n_buckets + s.n_excess;
     int t1[4], t2[4], e[4];
 #pragma unroll
@@ -234,23 +196,19 @@ __global__ __launch_bounds__(SWEEP_THREADS) void alloc_count_kernel(TsdfState s,
 }
 
 // single workgroup: exclusive scan of up to two arrays of per-block counts, totals to out_tot[0..1]
-__global__ __launch_bounds__(SCAN_THREADS) void scan_counts_kernel(int nblk, int32_t* __restrict__ a, int32_t* __restrict__ b,
+__global__ __launch_bounds__(SCAN_THREADS) void scan_counts_kernel(TsdfState s, int32_t* __restrict__ a, int32_t* __restrict__ b,
                                                                   int32_t* __restrict__ out_tot, const ViewRec* __restrict__ views) {
     GPS_FRAME_PRIO();
-    __shared__ int ws[17];
+    __shared__ int ws[SCAN_THREADS / 64 + 1];
     if (views) {  // free-view batch: the sweep counts and the list length of view blockIdx.z
-        a = views[blockIdx.z].scratch + 2 * nblk; b = nullptr; out_tot = views[blockIdx.z].counters + GPS_TSDF_N_VISIBLE_FREE;
+        apply_view(s, views[blockIdx.z]);
+        a = sweep_counts(s, 2); b = nullptr; out_tot = s.counters + GPS_TSDF_N_VISIBLE_FREE;
     }
-    const int per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int lo = min(nblk, (int)threadIdx.x * per), hi = min(nblk, lo + per);
+    const int nblk = sweep_blocks(s);
     for (int which = 0; which < 2; which++) {
         int32_t* arr = which == 0 ? a : b;
         if (arr == nullptr) continue;
-        int sum = 0;
-        for (int k = lo; k < hi; k++) sum += arr[k];
-        int total;
-        int run = block_excl_scan_1024(sum, ws, total);
-        for (int k = lo; k < hi; k++) { int v = arr[k]; arr[k] = run; run += v; }
+        const int total = block_scan_counts<SCAN_THREADS>(arr, nblk, ws);
         if (threadIdx.x == 0) out_tot[which] = total;
     }
 }
@@ -259,7 +217,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void alloc_apply_kernel(TsdfState s,
                                                                    const int32_t* __restrict__ blk2, uint32_t* __restrict__ bits) {
     GPS_FRAME_PRIO();
     __shared__ int ws[5];
-    const int idx0 = blockIdx.x * SWEEP + threadIdx.x * SLOTS_PER_THREAD;
+    const int idx0 = blockIdx.x * SWEEP_SLOTS + threadIdx.x * SLOTS_PER_THREAD;
     const int n_total = s.n_buckets + s.n_excess;
     uint32_t prio[4];
     int t[4], t1[4], t2[4], c1[4], c2[4];
@@ -326,12 +284,10 @@ __global__ __launch_bounds__(SWEEP_THREADS) void alloc_apply_kernel(TsdfState s,
     }
 }
 
-// visibility predicates for the two ordered compactions
-enum { VIS_LIVE = 0, VIS_FREE = 1 };
-
+// the predicates of the ordered compactions (SlotPredicate, tsdf_sweep.hpp)
 template <int MODE>
 __device__ __forceinline__ bool slot_visible(const TsdfState& s, const Mat4& M, int idx, bool update) {
-    if (MODE == VIS_LIVE) {
+    if (MODE == SLOT_VISIBLE_LIVE) {
         // CPU.tpp:268-306: type 3 (visible last frame) is re-tested against the frustum, types 1/2 stay
         uint8_t vt = s.visible_type[idx];
         if (vt == 3) {
@@ -340,10 +296,12 @@ __device__ __forceinline__ bool slot_visible(const TsdfState& s, const Mat4& M, 
             if (update) s.visible_type[idx] = vt;
         }
         return vt > 0;
-    } else {
+    } else if (MODE == SLOT_VISIBLE_FREE) {
         // Visualisation CPU.tpp:36-74 / buildCompleteVisibleList_device: every allocated block inside the frustum
         const HashEntry he = load_entry(s.hash, idx);
         return he.ptr >= 0 && block_visible(s, M, he.x, he.y, he.z);
+    } else {
+        return s.hash[idx].ptr >= 0;  // SLOT_ALLOCATED (findAllocateBlocks, ITMMeshingEngine_CUDA.tcu:101-110)
     }
 }
 
@@ -352,10 +310,10 @@ __global__ __launch_bounds__(SWEEP_THREADS) void visible_count_kernel(TsdfState 
                                                                      uint8_t* __restrict__ flags, const ViewRec* __restrict__ views) {
     GPS_FRAME_PRIO();
     __shared__ int ws[5];
-    if (views) { apply_view(s, views[blockIdx.z]); M = views[blockIdx.z].M; blk = sweep_counts(s); flags = sweep_flags(s); }
-    const int idx0 = blockIdx.x * SWEEP + threadIdx.x * SLOTS_PER_THREAD;
+    if (views) { apply_view(s, views[blockIdx.z]); M = views[blockIdx.z].M; blk = sweep_counts(s, 2); flags = sweep_flags(s); }
+    const int idx0 = blockIdx.x * SWEEP_SLOTS + threadIdx.x * SLOTS_PER_THREAD;
     const int n_total = s.n_buckets + s.n_excess;
-    if (MODE == VIS_LIVE && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (MODE == SLOT_VISIBLE_LIVE && blockIdx.x == 0 && threadIdx.x == 0) {
         // fold the allocation bookkeeping of this frame into the counters (ordered after alloc_apply)
         s.counters[GPS_TSDF_LAST_FREE_BLOCK] -= s.counters[GPS_TSDF_SCRATCH0];
         s.counters[GPS_TSDF_LAST_FREE_EXCESS] -= s.counters[GPS_TSDF_SCRATCH1];
@@ -379,8 +337,8 @@ __global__ __launch_bounds__(SWEEP_THREADS) void visible_write_kernel(TsdfState 
                                                                      const ViewRec* __restrict__ views) {
     GPS_FRAME_PRIO();
     __shared__ int ws[5];
-    if (views) { apply_view(s, views[blockIdx.z]); blk = sweep_counts(s); flags = sweep_flags(s); out_ids = s.fv_visible_ids; }
-    const int idx0 = blockIdx.x * SWEEP + threadIdx.x * SLOTS_PER_THREAD;
+    if (views) { apply_view(s, views[blockIdx.z]); blk = sweep_counts(s, 2); flags = sweep_flags(s); out_ids = s.fv_visible_ids; }
+    const int idx0 = blockIdx.x * SWEEP_SLOTS + threadIdx.x * SLOTS_PER_THREAD;
     const int n_total = s.n_buckets + s.n_excess;
     int v[4], e[4];
 #pragma unroll
@@ -624,26 +582,19 @@ static int allocate_impl(const gps_tsdf_state* sp, const float* M, const float* 
     Mat4 m = load_mat(M), im = load_mat(invM);
     hipStream_t st = (hipStream_t)stream;
     const int P = s.width * s.height;
-    const int n_total = s.n_buckets + s.n_excess;
-    const int nblk = gps_div_up(n_total, SWEEP);
-    int32_t* blk1 = s.scan_scratch;
-    int32_t* blk2 = s.scan_scratch + nblk;
-    int32_t* blkv = s.scan_scratch + 2 * nblk;
-    int32_t* tot = s.scan_scratch + 3 * nblk;  // [2] totals scratch
+    const int nblk = sweep_blocks(s);
+    int32_t* blk1 = sweep_counts(s, 0);
+    int32_t* blk2 = sweep_counts(s, 1);
     mark_previous_visible_kernel<<<256, 256, 0, st>>>(s, (uint8_t)(reset_visible ? 0 : 3));
     alloc_request_kernel<<<gps_div_up(P, 256), 256, 0, st>>>(s, im, allocate);
     if (allocate) {   // (without requests the three launches below would find nothing to do)
         alloc_count_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, blk1, blk2);
-        scan_counts_kernel<<<1, SCAN_THREADS, 0, st>>>(nblk, blk1, blk2, tot, nullptr);
+        scan_counts_kernel<<<1, SCAN_THREADS, 0, st>>>(s, blk1, blk2, sweep_totals(s), nullptr);
         alloc_apply_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, im, blk1, blk2, bucket_bits(s));
     }
-    // ordered visible list (byte flags live behind the per-block counts in scan_scratch)
-    uint8_t* flags = reinterpret_cast<uint8_t*>(s.scan_scratch + 3 * nblk + 16);
-    visible_count_kernel<VIS_LIVE><<<nblk, SWEEP_THREADS, 0, st>>>(s, m, blkv, flags, nullptr);
-    scan_counts_kernel<<<1, SCAN_THREADS, 0, st>>>(nblk, blkv, nullptr, &s.counters[GPS_TSDF_N_VISIBLE], nullptr);
-    visible_write_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, blkv, flags, s.visible_ids, s.n_blocks, nullptr);
     GPS_LAUNCH_CHECK();
-    return GPS_OK;
+    return sweep_slots(s, SLOT_VISIBLE_LIVE, m, sweep_counts(s, 2), sweep_flags(s), s.visible_ids, s.n_blocks,
+                       &s.counters[GPS_TSDF_N_VISIBLE], 0, nullptr, st);
 }
 
 int gps_tsdf_allocate(const gps_tsdf_state* sp, const float* M, const float* invM, gps_stream stream) {
@@ -661,27 +612,22 @@ int gps_tsdf_find_visible(const gps_tsdf_state* sp, const float* M, gps_stream s
     TsdfState s = *sp;
     Mat4 m = load_mat(M);
     hipStream_t st = (hipStream_t)stream;
-    const int n_total = s.n_buckets + s.n_excess;
-    const int nblk = gps_div_up(n_total, SWEEP);
-    int32_t* blkv = s.scan_scratch + 2 * nblk;
-    uint8_t* flags = reinterpret_cast<uint8_t*>(s.scan_scratch + 3 * nblk + 16);
-    visible_count_kernel<VIS_FREE><<<nblk, SWEEP_THREADS, 0, st>>>(s, m, blkv, flags, nullptr);
-    scan_counts_kernel<<<1, SCAN_THREADS, 0, st>>>(nblk, blkv, nullptr, &s.counters[GPS_TSDF_N_VISIBLE_FREE], nullptr);
-    visible_write_kernel<<<nblk, SWEEP_THREADS, 0, st>>>(s, blkv, flags, s.fv_visible_ids, s.n_blocks, nullptr);
-    GPS_LAUNCH_CHECK();
-    return GPS_OK;
+    return sweep_slots(s, SLOT_VISIBLE_FREE, m, sweep_counts(s, 2), sweep_flags(s), s.fv_visible_ids, s.n_blocks,
+                       &s.counters[GPS_TSDF_N_VISIBLE_FREE], 0, nullptr, st);
 }
 
 }  // extern "C"
 
 namespace gpst {
-// ordered visible lists of n free views in three launches (grid.z = view)
-int find_visible_batch(const TsdfState& s, int n, const ViewRec* table, hipStream_t st) {
+int sweep_slots(const TsdfState& s, SlotPredicate pred, const Mat4& M, int32_t* counts, uint8_t* flags, int32_t* list, int cap,
+                int32_t* count, int n_views, const ViewRec* views, hipStream_t st) {
     const int nblk = sweep_blocks(s);
-    const Mat4 none = {};
-    visible_count_kernel<VIS_FREE><<<dim3(nblk, 1, n), SWEEP_THREADS, 0, st>>>(s, none, nullptr, nullptr, table);
-    scan_counts_kernel<<<dim3(1, 1, n), SCAN_THREADS, 0, st>>>(nblk, nullptr, nullptr, nullptr, table);
-    visible_write_kernel<<<dim3(nblk, 1, n), SWEEP_THREADS, 0, st>>>(s, nullptr, nullptr, nullptr, s.n_blocks, table);
+    const dim3 grid(nblk, 1, views ? n_views : 1), one(1, 1, views ? n_views : 1);
+    if (pred == SLOT_VISIBLE_LIVE) visible_count_kernel<SLOT_VISIBLE_LIVE><<<grid, SWEEP_THREADS, 0, st>>>(s, M, counts, flags, views);
+    else if (pred == SLOT_VISIBLE_FREE) visible_count_kernel<SLOT_VISIBLE_FREE><<<grid, SWEEP_THREADS, 0, st>>>(s, M, counts, flags, views);
+    else visible_count_kernel<SLOT_ALLOCATED><<<grid, SWEEP_THREADS, 0, st>>>(s, M, counts, flags, views);
+    scan_counts_kernel<<<one, SCAN_THREADS, 0, st>>>(s, counts, nullptr, count, views);
+    visible_write_kernel<<<grid, SWEEP_THREADS, 0, st>>>(s, counts, flags, list, cap, views);
     return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
 }
 }  // namespace gpst

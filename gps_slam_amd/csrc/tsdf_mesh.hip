@@ -5,7 +5,7 @@
 //
 // The reference's CUDA engine appends triangles with one global atomicAdd each, so their order changes from run to run;
 // its CPU engine emits them in (hash entry, z, y, x, case-table) order.  Here the order is the CPU engine's, every run:
-//   1. ordered list of allocated hash entries (count per 1024 slots -> scan -> write),
+//   1. ordered list of allocated hash entries (the ordered slot sweep of tsdf_sweep.hpp: count -> scan -> write),
 //   2. one workgroup per allocated block stages the 9x9x9 voxel neighbourhood (own block + the 7 blocks behind its +x/+y/+z
 //      faces, resolved by 8 hash walks per block instead of 8 per voxel) in LDS and counts its triangles,
 //   3. exclusive scan of the per-block counts,
@@ -13,7 +13,7 @@
 // Nothing synchronises with the host; the triangle count stays on the device.  Float arithmetic follows the CPU engine
 // operation by operation (this file is built with -ffp-contract=off like the other TSDF kernels): positions and colours
 // are bit-equal to the restatement in oracle/tsdf_oracle.c, which is bit-equal to the reference CPU engine.
-#include "tsdf_common.hpp"
+#include "tsdf_sweep.hpp"
 
 using namespace gpst;
 
@@ -22,77 +22,17 @@ namespace {
 #include "mc_cases.inc"
 __device__ const unsigned long long mc_cases_dev[256] = GPS_MC_CASES_INIT;
 
-constexpr int SLOTS = 1024;   // hash slots per workgroup of the list sweeps
 constexpr int NB = 9;         // staged neighbourhood edge
 constexpr int NB3 = NB * NB * NB;
 constexpr int STAGE = 256;    // triangles per LDS staging round of the emit pass (21.5 KB)
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int n = __shfl_up(v, o, 64);
-        if (lane >= o) v += n;
-    }
-    return v;
-}
-
-// exclusive scan over the NT threads of the workgroup; ws needs NT/64 + 1 ints
-template <int NT>
-__device__ __forceinline__ int block_excl_scan(int v, int* ws, int& total) {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(v);
-    if (lane == 63) ws[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        const int sv = lane < NW ? ws[lane] : 0;
-        const int si = wave_incl_scan(sv);
-        if (lane < NW) ws[lane] = si - sv;
-        if (lane == 63) ws[NW] = si;
-    }
-    __syncthreads();
-    const int r = ws[wave] + incl - v;
-    total = ws[NW];
-    __syncthreads();
-    return r;
-}
-
-// ---- 1. ordered list of allocated entries
-__global__ __launch_bounds__(SLOTS) void mesh_entries_count_kernel(TsdfState s, int32_t* __restrict__ blk) {
-    __shared__ int ws[17];
-    const int idx = blockIdx.x * SLOTS + threadIdx.x;
-    const int n_total = s.n_buckets + s.n_excess;
-    const int has = idx < n_total && s.hash[idx].ptr >= 0;
-    int tot;
-    block_excl_scan<SLOTS>(has, ws, tot);
-    if (threadIdx.x == 0) blk[blockIdx.x] = tot;
-}
-
-// single workgroup: in-place exclusive scan of n counts, total to *out_total
-__global__ __launch_bounds__(1024) void mesh_scan_kernel(const int32_t* __restrict__ n_ptr, int n_fixed, int32_t* __restrict__ arr,
-                                                        int32_t* __restrict__ out_total) {
-    __shared__ int ws[17];
-    const int n = n_ptr ? *n_ptr : n_fixed;
-    const int per = (n + 1023) / 1024;
-    const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
-    int sum = 0;
-    for (int k = lo; k < hi; k++) sum += arr[k];
-    int total;
-    int run = block_excl_scan<1024>(sum, ws, total);
-    for (int k = lo; k < hi; k++) { const int v = arr[k]; arr[k] = run; run += v; }
+// single workgroup: in-place exclusive scan of the *n_ptr per-block triangle counts, total to *out_total
+constexpr int SCAN_THREADS = 1024;
+__global__ __launch_bounds__(SCAN_THREADS) void mesh_scan_kernel(const int32_t* __restrict__ n_ptr, int32_t* __restrict__ arr,
+                                                                int32_t* __restrict__ out_total) {
+    __shared__ int ws[SCAN_THREADS / 64 + 1];
+    const int total = block_scan_counts<SCAN_THREADS>(arr, *n_ptr, ws);
     if (threadIdx.x == 0) *out_total = total;
-}
-
-__global__ __launch_bounds__(SLOTS) void mesh_entries_write_kernel(TsdfState s, const int32_t* __restrict__ blk,
-                                                                  int32_t* __restrict__ list) {
-    __shared__ int ws[17];
-    const int idx = blockIdx.x * SLOTS + threadIdx.x;
-    const int n_total = s.n_buckets + s.n_excess;
-    const int has = idx < n_total && s.hash[idx].ptr >= 0;
-    int tot;
-    const int pos = blk[blockIdx.x] + block_excl_scan<SLOTS>(has, ws, tot);
-    if (has && pos < s.n_blocks) list[pos] = idx;
 }
 
 // ---- 2./4. per-block marching cubes
@@ -237,13 +177,13 @@ __global__ void mesh_finish_kernel(const int32_t* __restrict__ total, int64_t ma
     counts[1] = t;                                                                         // triangles the scene holds
 }
 
-struct MeshWs { int32_t *blk, *list, *tri, *n_list, *total; };
+struct MeshWs { int32_t *blk; uint8_t* flags; int32_t *list, *tri, *n_list, *total; };
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline int64_t carve_ws(MeshWs* w, char* base, const TsdfState& s) {
-    const int nblk = gps_div_up(s.n_buckets + s.n_excess, SLOTS);
     int64_t off = 0;
     auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align16(bytes); return p; };
-    w->blk = (int32_t*)take((int64_t)nblk * 4);
+    w->blk = (int32_t*)take((int64_t)sweep_blocks(s) * 4);   // the entry sweep's own counts and flag bytes: the scene's
+    w->flags = (uint8_t*)take((int64_t)s.n_buckets + s.n_excess);   // scan_scratch may be in use by the frame chain on another stream
     w->list = (int32_t*)take((int64_t)s.n_blocks * 4);
     w->tri = (int32_t*)take((int64_t)s.n_blocks * 4);
     w->n_list = (int32_t*)take(16);
@@ -271,13 +211,12 @@ int gps_tsdf_mesh_scene(const gps_tsdf_state* sp, int64_t max_triangles, float* 
     MeshWs w;
     if (workspace_bytes < carve_ws(&w, (char*)workspace, s)) return GPS_ERR_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = gps_div_up(s.n_buckets + s.n_excess, SLOTS);
-    mesh_entries_count_kernel<<<nblk, SLOTS, 0, st>>>(s, w.blk);
-    mesh_scan_kernel<<<1, 1024, 0, st>>>(nullptr, nblk, w.blk, w.n_list);
-    mesh_entries_write_kernel<<<nblk, SLOTS, 0, st>>>(s, w.blk, w.list);
+    const Mat4 none = {};
+    const int r = sweep_slots(s, SLOT_ALLOCATED, none, w.blk, w.flags, w.list, s.n_blocks, w.n_list, 0, nullptr, st);
+    if (r != GPS_OK) return r;
     const int grid = 4096;  // grid-stride over the allocated blocks (their number is only known on the device)
     mesh_block_kernel<false><<<grid, 512, 0, st>>>(s, w.list, w.n_list, w.tri, nullptr, max_triangles, nullptr);
-    mesh_scan_kernel<<<1, 1024, 0, st>>>(w.n_list, 0, w.tri, w.total);
+    mesh_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(w.n_list, w.tri, w.total);
     mesh_block_kernel<true><<<grid, 512, 0, st>>>(s, w.list, w.n_list, nullptr, w.tri, max_triangles, triangles);
     mesh_finish_kernel<<<1, 1, 0, st>>>(w.total, max_triangles, counts);
     GPS_LAUNCH_CHECK();

@@ -15,9 +15,9 @@
 #include <math.h>
 
 #include "launch_timing.hpp"
-#include "tsdf_common.hpp"
 #include "tsdf_normals.hpp"
 #include "tsdf_pose.hpp"
+#include "tsdf_sweep.hpp"
 #include "tsdf_voxel.hpp"
 #include "wave_reduce.hpp"
 
@@ -168,9 +168,6 @@ __global__ __launch_bounds__(256) void expected_depths_reduce_kernel(TsdfState s
 #define GPS_RAYCAST_SKIP 5
 #endif
 GPS_TUNABLE_REPORT(GPS_RAYCAST_SKIP, 5);
-#ifdef GPS_ED_REDUCE_LAUNCH   // (probe builds: pass B of the expected depths as its own launch)
-GPS_SWITCH_REPORT(GPS_ED_REDUCE_LAUNCH);
-#endif
 constexpr int SKIP = GPS_RAYCAST_SKIP;
 #ifndef GPS_RAYCAST_RAYS_PER_WAVE
 #define GPS_RAYCAST_RAYS_PER_WAVE 64
@@ -553,8 +550,6 @@ __global__ __launch_bounds__(256) void view_init_kernel(int P, float2* __restric
 
 }  // namespace
 
-namespace gpst { int find_visible_batch(const TsdfState& s, int n, const ViewRec* table, hipStream_t st); }
-
 extern "C" {
 
 int64_t gps_tsdf_view_table_bytes(int n_views) {
@@ -598,21 +593,16 @@ int gps_tsdf_free_raycast_batch(const gps_tsdf_state* sp, int n_views, const gps
     ViewRec* tab = reinterpret_cast<ViewRec*>(table);
     upload_views_kernel<<<1, 256, 0, st>>>(t, n_views, tab);
     int r;
-    if ((r = gpst::find_visible_batch(s, n_views, tab, st)) != GPS_OK) return r;
+    const Mat4 none = {};
+    if ((r = sweep_slots(s, SLOT_VISIBLE_FREE, none, nullptr, nullptr, nullptr, s.n_blocks, nullptr, n_views, tab, st)) != GPS_OK) return r;
     const int sw = s.width / MINMAX_SUB + 2, sh = s.height / MINMAX_SUB + 2;
     const size_t lds = (size_t)sw * sh * sizeof(uint2);
     GPS_REQUIRE(lds <= 160 * 1024);
-    const Mat4 none = {};
     expected_depths_partial_kernel<<<dim3(ED_GROUPS, 1, n_views), ED_THREADS, lds, st>>>(s, none, nullptr, GPS_TSDF_N_VISIBLE_FREE, sw,
                                                                                      sh, nullptr, tab);
     const dim3 grid(gps_div_up(s.width, 2 * RC_PW), gps_div_up(s.height, 2 * RC_PH), n_views);   // (the raycaster's)
-#ifdef GPS_ED_REDUCE_LAUNCH
-    expected_depths_reduce_kernel<<<dim3(gps_div_up(sw * sh, 256), 1, n_views), 256, 0, st>>>(s, sw, sh, ED_GROUPS, nullptr, nullptr, tab);
-    raycast_kernel<false><<<grid, 256, 0, st>>>(s, none, nullptr, nullptr, bucket_bits(s), tab, nullptr, 0, 0, nullptr, gps::LaunchStamp{nullptr});
-#else
     // (pass B of the expected depths rides in the raycaster)
     raycast_kernel<false><<<grid, 256, 0, st>>>(s, none, nullptr, nullptr, bucket_bits(s), tab, nullptr, sw, sh, nullptr, gps::LaunchStamp{nullptr});
-#endif
     colour_kernel<<<dim3(gps_div_up(s.width, 16), gps_div_up(s.height, 16), n_views), 256, 0, st>>>(s, nullptr, nullptr, tab, gps::LaunchStamp{nullptr});
     GPS_LAUNCH_CHECK();
     return GPS_OK;
@@ -630,10 +620,7 @@ static int expected_depths_impl(const gps_tsdf_state* sp, const float* M, int fr
     const int sw = s.width / MINMAX_SUB + 2, sh = s.height / MINMAX_SUB + 2;
     const size_t lds = (size_t)sw * sh * sizeof(uint2);
     GPS_REQUIRE(lds <= 160 * 1024);
-    const int n_total = s.n_buckets + s.n_excess;
-    const int nblk = gps_div_up(n_total, 1024);
-    // partial images live behind the sweep scratch (3*nblk + 16 ints + n_total flag bytes), see gps_tsdf_scratch_bytes
-    uint2* partial = reinterpret_cast<uint2*>(s.scan_scratch + 3 * nblk + 16 + (n_total + 3) / 4 + 2);
+    uint2* partial = minmax_partials(s);
     float2* mm = reinterpret_cast<float2*>(free_view ? s.fv_minmax : s.minmax);
     expected_depths_partial_kernel<<<ED_GROUPS, ED_THREADS, lds, st>>>(s, load_mat(M), free_view ? s.fv_visible_ids : s.visible_ids,
                                                                 free_view ? GPS_TSDF_N_VISIBLE_FREE : GPS_TSDF_N_VISIBLE,
@@ -655,13 +642,9 @@ int gps_tsdf_expected_depths_partial(const gps_tsdf_state* sp, const float* M, i
 
 int64_t gps_tsdf_scratch_bytes(int width, int height, int n_buckets, int n_excess) {
     if (width <= 0 || height <= 0 || n_buckets <= 0 || n_excess <= 0) return GPS_ERR_ARG;
-    const int64_t n_total = (int64_t)n_buckets + n_excess;
-    const int64_t nblk = (n_total + 1023) / 1024;
-    const int64_t sw = width / MINMAX_SUB + 2, sh = height / MINMAX_SUB + 2;
-    (void)nblk; (void)sw; (void)sh;
     gps_tsdf_state t = {};
     t.width = width; t.height = height; t.n_buckets = n_buckets; t.n_excess = n_excess;
-    return 4 * (ray_stats_offset_words(t) + 4 + 4 * (int64_t)ray_stat_waves(t));
+    return 4 * scratch_layout(t).total;
 }
 
 static int raycast_impl(const gps_tsdf_state* sp, const float* invM, int free_view, int update_visible, bool reduce_here,
@@ -673,9 +656,7 @@ static int raycast_impl(const gps_tsdf_state* sp, const float* invM, int free_vi
     float2* mm = reinterpret_cast<float2*>(free_view ? s.fv_minmax : s.minmax);
     float4* rays = reinterpret_cast<float4*>(free_view ? s.fv_raycast : s.raycast);
     const int sw = s.width / MINMAX_SUB + 2, sh = s.height / MINMAX_SUB + 2;
-    const int n_total = s.n_buckets + s.n_excess, nblk = gps_div_up(n_total, 1024);
-    // (where expected_depths_impl put the partial images)
-    const uint2* partial = reduce_here ? reinterpret_cast<const uint2*>(s.scan_scratch + 3 * nblk + 16 + (n_total + 3) / 4 + 2) : nullptr;
+    const uint2* partial = reduce_here ? minmax_partials(s) : nullptr;   // (where expected_depths_impl put the partial images)
     const ViewRec* no_table = nullptr;
     if (update_visible)
         gps::launch_kernel(gps::TK_RAYCAST, 0, raycast_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, s, load_mat(invM), (const float2*)mm, rays,
@@ -697,13 +678,8 @@ int gps_tsdf_raycast(const gps_tsdf_state* sp, const float* invM, int free_view,
 int gps_tsdf_expected_depths_and_raycast(const gps_tsdf_state* sp, const float* M, const float* invM, int free_view,
                                          int update_visible, gps_stream stream) {
     GPS_ENTER();
-#ifdef GPS_ED_REDUCE_LAUNCH   // (probe builds: the three-launch form, for an A/B)
-    const int r = expected_depths_impl(sp, M, free_view, true, stream);
-    return r != GPS_OK ? r : raycast_impl(sp, invM, free_view, update_visible, false, stream);
-#else
     const int r = expected_depths_impl(sp, M, free_view, false, stream);
     return r != GPS_OK ? r : raycast_impl(sp, invM, free_view, update_visible, true, stream);
-#endif
 }
 
 int gps_tsdf_ray_stats(const gps_tsdf_state* sp, gps_stream stream) {

@@ -1387,11 +1387,6 @@ int64_t gps_track_scratch_bytes(int width, int height) {
     return (int64_t)carve(nullptr, nullptr, width, height);
 }
 
-static inline double wall_ms() {
-    timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
-    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
-
 // PrepareForEvaluation: the depth pyramid (the scene side, the ICP maps, always stays at full resolution) and the per-level
 // constants of the evaluations (pa.tab_vals), in one launch
 static int launch_prepare(const gps_tsdf_state* sp, const TsdfState& s, const gps_track_config* c, gps_track_state* ts,

@@ -37,6 +37,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.gps_build_flags() == b"", lib.gps_build_flags()
 
 
+def test_tsdf_scratch_bytes_are_the_recorded_ones():
+    """gps_tsdf_scratch_bytes is visible to callers (per-view scratch buffers, saved state): the layout function behind it must
+    return what the library returned before the layout had one description (tests/golden/make_tsdf_scratch_bytes_golden.py:
+    five image sizes x four table sizes, ragged and minimal ones included)."""
+    import json
+    from gps_slam_amd import _lib
+    lib = _lib.load_library()
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "tsdf_scratch_bytes.json")))
+    assert len(table["rows"]) == 20
+    for w, h, n_buckets, n_excess, want in table["rows"]:
+        assert lib.gps_tsdf_scratch_bytes(w, h, n_buckets, n_excess) == want, (w, h, n_buckets, n_excess)
+
+
 def test_no_wrong_result_experiment_paths_in_the_product_kernels():
     """Timing experiments that produce wrong results live in tools/probe/ (or in the history), not behind macros in csrc/."""
     import re
