@@ -94,6 +94,8 @@ PROTOTYPES = {
     "gps_raster_raw_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "gps_raster_raw_bwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                  vp]),
+    "gps_raster_raw_bwd_ordered": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp]),
     "gps_raster_ges_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]),
     "gps_raster_ges_bwd_gs": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp,
                                     i32, vp]),
@@ -215,6 +217,10 @@ PROTOTYPES = {
     "gps_compact_mask_workspace_bytes": (i64, [i32]),
     "gps_compact_mask": (i32, [i32, vp, vp, vp, vp, vp, i64, vp]),
     "gps_gather_pixels": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gps_densify_accumulate": (i32, [i32, vp, vp, i32, i32, vp, vp, vp]),
+    "gps_densify_plan_workspace_bytes": (i64, [i32]),
+    "gps_densify_plan": (i32, [i32, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "gps_densify_apply": (i32, [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gps_splat_can_prefetch": (i32, [C.POINTER(SplatStep)]),
     "gps_splat_discard_prefetch": (i32, [C.POINTER(SplatStep), vp]),
     "gps_splat_render": (i32, [C.POINTER(SplatStep), vp]),

@@ -120,17 +120,23 @@ __global__ __launch_bounds__(256) void zero_raw_grads_kernel(int N, float* __res
     }
 }
 
-template <bool ABS>
+// ORDERED: the same walk with a reduction whose order is fixed, for callers that need two runs to give the same bits.  Each
+// wave keeps its own LDS gradient tile (plain stores: a (Gaussian, value) pair is written by one lane of the wave, once per
+// batch), the batch's closing pass sums the four in wave order and writes the tile's totals per INTERSECTION
+// (isect_grads[n_isects][12], every row of the tile's range, zeros where the walk never came), and raw_gather_isect_grads_kernel
+// sums a Gaussian's rows in ascending intersection order.  No float atomic anywhere; 60 KB of LDS instead of 24.
+template <bool ABS, bool ORDERED>
 __global__ __launch_bounds__(256) void raster_raw_bwd_kernel(
     const float2* __restrict__ means2d, const float* __restrict__ conics, const float4* __restrict__ colors,
     const float* __restrict__ opacities, const float* __restrict__ backgrounds, int W, int H, int tw, int th,
     const int32_t* __restrict__ tile_offsets, const int32_t* __restrict__ flatten_ids, const int64_t* __restrict__ counts,
     const float* __restrict__ render_alphas, const int32_t* __restrict__ last_ids, const float4* __restrict__ v_render_colors,
     const float* __restrict__ v_render_alphas, float* __restrict__ v_means2d_abs, float* __restrict__ v_means2d,
-    float* __restrict__ v_conics, float* __restrict__ v_colors, float* __restrict__ v_opacities) {
+    float* __restrict__ v_conics, float* __restrict__ v_colors, float* __restrict__ v_opacities, float* __restrict__ isect_grads) {
     constexpr int NG = 12;  // rgb d | conic abc | xy | opac | (|x| |y|)
+    constexpr int SLABS = ORDERED ? 4 : 1;   // gradient tiles: one per wave, or one shared through ds_add_f32
     __shared__ RawRec recs[RAW_BATCH];
-    __shared__ float grad[RAW_BATCH][NG];
+    __shared__ float grad[SLABS * RAW_BATCH][NG];
     __shared__ int tile_last;
     const int tile_id = blockIdx.x;
     const int ty = tile_id / tw, tx = tile_id - ty * tw;
@@ -164,11 +170,14 @@ __global__ __launch_bounds__(256) void raster_raw_bwd_kernel(
     }
     __syncthreads();
     const int walk_end = min(range_end - 1, tile_last);  // inclusive
+    const int slab = ORDERED ? (tid >> 6) * RAW_BATCH : 0;
+    if (ORDERED)   // the intersections behind the walk's start receive nothing
+        for (int k = max(walk_end + 1, range_start) * NG + tid; k < range_end * NG; k += 256) isect_grads[k] = 0.f;
     for (int batch_end = walk_end; batch_end >= range_start; batch_end -= RAW_BATCH) {
         __syncthreads();
         const int n = min(RAW_BATCH, batch_end + 1 - range_start);
         if (tid < n) recs[tid] = load_rec(flatten_ids[batch_end - tid], means2d, conics, colors, opacities);  // [0] = furthest back
-        for (int k = tid; k < RAW_BATCH * NG; k += 256) (&grad[0][0])[k] = 0.f;
+        for (int k = tid; k < SLABS * RAW_BATCH * NG; k += 256) (&grad[0][0])[k] = 0.f;
         __syncthreads();
         for (int t = 0; t < n; ++t) {
             const RawRec r = recs[t];
@@ -206,20 +215,36 @@ __global__ __launch_bounds__(256) void raster_raw_bwd_kernel(
             const float z0 = reduce4(g0, g1, g2, g3);
             const float z1 = reduce4(g4, g5, g6, g7);
             if ((lane & 15) == 15) {
-                float* gt = &grad[t][row_slot];
-                atomicAdd(gt, z0);
-                atomicAdd(gt + 4, z1);
+                float* gt = &grad[slab + t][row_slot];
+                if (ORDERED) { gt[0] = z0; gt[4] = z1; }
+                else { atomicAdd(gt, z0); atomicAdd(gt + 4, z1); }
             }
             if (ABS) {
                 const float z2 = reduce4(g8, g9, fabsf(g7), fabsf(g8));  // rows: g8 |g7| g9 |g8| -> slots 8 10 9 11
-                if ((lane & 15) == 15) atomicAdd(&grad[t][8 + row_slot], z2);
+                if ((lane & 15) == 15) {
+                    if (ORDERED) grad[slab + t][8 + row_slot] = z2;
+                    else atomicAdd(&grad[t][8 + row_slot], z2);
+                }
             } else {
                 // two values left: one per half-wave, row sums, then row 0 -> 1 and row 2 -> 3 (row_bcast15)
                 const float z2 = dpp_add_masked<0x142, 0xA>(row_sum_to_lane15(sum_halves(g8, g9)));
-                if ((lane & 31) == 31) atomicAdd(&grad[t][8 + (lane >> 5)], z2);
+                if ((lane & 31) == 31) {
+                    if (ORDERED) grad[slab + t][8 + (lane >> 5)] = z2;
+                    else atomicAdd(&grad[t][8 + (lane >> 5)], z2);
+                }
             }
         }
         __syncthreads();
+        if (ORDERED) {   // the four waves' tiles in wave order, one row per intersection of the batch
+            if (tid < n) {
+                float* out = isect_grads + (size_t)(batch_end - tid) * NG;
+#pragma unroll
+                for (int c = 0; c < NG; c++)
+                    out[c] = ((grad[tid][c] + grad[(SLABS > 1 ? 1 : 0) * RAW_BATCH + tid][c]) + grad[(SLABS > 1 ? 2 : 0) * RAW_BATCH + tid][c]) +
+                             grad[(SLABS > 1 ? 3 : 0) * RAW_BATCH + tid][c];
+            }
+            continue;
+        }
         // one pass per batch: the tile's totals go to global memory, 10 (12) atomics per Gaussian that received anything
         if (tid < n) {
             const int gid = recs[tid].id;
@@ -243,6 +268,38 @@ __global__ __launch_bounds__(256) void raster_raw_bwd_kernel(
             }
         }
     }
+}
+
+// One thread per Gaussian: the rows of isect_grads that belong to it, summed in ascending intersection order.  order[p]: the
+// intersections sorted by Gaussian id, ties in ascending index (a stable sort of flatten_ids).
+template <bool ABS>
+__global__ __launch_bounds__(256) void raw_gather_isect_grads_kernel(int N, int64_t n_isects, const int32_t* __restrict__ flatten_ids,
+                                                                    const int32_t* __restrict__ order, const float* __restrict__ isect_grads,
+                                                                    float* __restrict__ v_means2d_abs, float* __restrict__ v_means2d,
+                                                                    float* __restrict__ v_conics, float* __restrict__ v_colors,
+                                                                    float* __restrict__ v_opacities) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= N) return;
+    int64_t lo = 0, hi = n_isects;   // first position whose Gaussian id is >= g
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (flatten_ids[order[mid]] < g) lo = mid + 1; else hi = mid;
+    }
+    float a[12];
+#pragma unroll
+    for (int c = 0; c < 12; c++) a[c] = 0.f;
+    for (int64_t p = lo; p < n_isects; p++) {
+        const int idx = order[p];
+        if (flatten_ids[idx] != g) break;
+        const float* row = isect_grads + (size_t)idx * 12;
+#pragma unroll
+        for (int c = 0; c < 12; c++) a[c] += row[c];
+    }
+    v_colors[4 * (size_t)g] = a[0]; v_colors[4 * (size_t)g + 1] = a[1]; v_colors[4 * (size_t)g + 2] = a[2]; v_colors[4 * (size_t)g + 3] = a[3];
+    v_conics[3 * (size_t)g] = a[4]; v_conics[3 * (size_t)g + 1] = a[5]; v_conics[3 * (size_t)g + 2] = a[6];
+    v_means2d[2 * (size_t)g] = a[7]; v_means2d[2 * (size_t)g + 1] = a[8];
+    v_opacities[g] = a[9];
+    if (ABS) { v_means2d_abs[2 * (size_t)g] = a[10]; v_means2d_abs[2 * (size_t)g + 1] = a[11]; }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -395,8 +452,37 @@ int gps_raster_raw_bwd(int N, const float* means2d, const float* conics, const f
 #define GPS_RAW_BWD_ARGS (const float2*)means2d, conics, (const float4*)colors, opacities, backgrounds, width, height, tw, th, \
                          tile_offsets, flatten_ids, counts, render_alphas, last_ids, (const float4*)v_render_colors,          \
                          v_render_alphas, v_means2d_abs, v_means2d, v_conics, v_colors, v_opacities
-    if (v_means2d_abs) raster_raw_bwd_kernel<true><<<tw * th, 256, 0, s>>>(GPS_RAW_BWD_ARGS);
-    else raster_raw_bwd_kernel<false><<<tw * th, 256, 0, s>>>(GPS_RAW_BWD_ARGS);
+    if (v_means2d_abs) raster_raw_bwd_kernel<true, false><<<tw * th, 256, 0, s>>>(GPS_RAW_BWD_ARGS, nullptr);
+    else raster_raw_bwd_kernel<false, false><<<tw * th, 256, 0, s>>>(GPS_RAW_BWD_ARGS, nullptr);
+    GPS_LAUNCH_CHECK();
+    return GPS_OK;
+}
+
+int gps_raster_raw_bwd_ordered(int N, const float* means2d, const float* conics, const float* colors, const float* opacities,
+                               const float* backgrounds, int width, int height, int tile_size, const int32_t* tile_offsets,
+                               const int32_t* flatten_ids, const int64_t* counts, int64_t n_isects, const int32_t* order,
+                               float* isect_grads, const float* render_alphas, const int32_t* last_ids, const float* v_render_colors,
+                               const float* v_render_alphas, float* v_means2d_abs, float* v_means2d, float* v_conics,
+                               float* v_colors, float* v_opacities, gps_stream stream) {
+    GPS_ENTER();
+    GPS_REQUIRE(N >= 0 && width > 0 && height > 0 && n_isects >= 0 && n_isects <= 0x7fffffff / 12);
+    GPS_REQUIRE(tile_size == 16);
+    if (N == 0) return GPS_OK;
+    GPS_REQUIRE(means2d && conics && colors && opacities && tile_offsets && counts && render_alphas && last_ids &&
+                v_render_colors && v_render_alphas && v_means2d && v_conics && v_colors && v_opacities);
+    GPS_REQUIRE(n_isects == 0 || (flatten_ids && order && isect_grads));
+    const int tw = gps_div_up(width, 16), th = gps_div_up(height, 16);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_isects > 0) {   // (counts[0] holds n_isects: the last tile's range ends there)
+        if (v_means2d_abs) raster_raw_bwd_kernel<true, true><<<tw * th, 256, 0, s>>>(GPS_RAW_BWD_ARGS, isect_grads);
+        else raster_raw_bwd_kernel<false, true><<<tw * th, 256, 0, s>>>(GPS_RAW_BWD_ARGS, isect_grads);
+    }
+    if (v_means2d_abs)
+        raw_gather_isect_grads_kernel<true><<<gps_div_up(N, 256), 256, 0, s>>>(N, n_isects, flatten_ids, order, isect_grads, v_means2d_abs,
+                                                                              v_means2d, v_conics, v_colors, v_opacities);
+    else
+        raw_gather_isect_grads_kernel<false><<<gps_div_up(N, 256), 256, 0, s>>>(N, n_isects, flatten_ids, order, isect_grads, nullptr,
+                                                                               v_means2d, v_conics, v_colors, v_opacities);
 #undef GPS_RAW_BWD_ARGS
     GPS_LAUNCH_CHECK();
     return GPS_OK;

@@ -200,6 +200,14 @@ PYBIND11_MODULE(_host, m) {
             s.configFields(dump, capacity);
             return dump.out;
         })
+        .def("flattenConfig", [](SLAMGaussianModel& s, const gpsh::Node& model_node) {
+            // what loadConfig(node) would read, as the flat route's dict; nothing is assigned or allocated
+            const gpsh::Config c = s.flattenConfig(model_node);
+            py::dict d;
+            for (const auto& kv : c.num) d[py::str(kv.first)] = kv.second;
+            for (const auto& kv : c.str) d[py::str(kv.first)] = kv.second;
+            return d;
+        })
         .def("saveParamsTensor", &SLAMGaussianModel::saveParamsTensor)
         .def("saveParamsPly", &SLAMGaussianModel::saveParamsPly)
         .def("loadParamsTensor", &SLAMGaussianModel::loadParamsTensor)
@@ -209,6 +217,7 @@ PYBIND11_MODULE(_host, m) {
             s.backgrounds = bg.has_value() ? *bg : torch::Tensor();
         })
         .def_readwrite("render_method", &SLAMGaussianModel::render_method)
+        .def_readwrite("ordered_raw_backward", &SLAMGaussianModel::ordered_raw_backward)
         .def("computeLoss", [](SLAMGaussianModel& s, TensorDict& r, const Camera& cam, const py::dict& w) {
             return s.computeLoss(r, cam, config_from_dict(w));
         })
@@ -242,6 +251,28 @@ PYBIND11_MODULE(_host, m) {
         .def("optimizersStep", &SLAMGaussianModel::optimizersStep)
         .def("optimizersZeroGrad", &SLAMGaussianModel::optimizersZeroGrad)
         .def("prunePoints", &SLAMGaussianModel::prunePoints)
+        .def("stepPostBackward", [](SLAMGaussianModel& s, TensorDict& r, const Camera& cam, float scene_scale, int curr_iter) {
+            s.stepPostBackward(r, cam, scene_scale, curr_iter);
+        }, py::arg("render_res"), py::arg("cam"), py::arg("scene_scale"), py::arg("curr_iter"))
+        .def("updateDensifyGrad", [](SLAMGaussianModel& s, TensorDict& r, const Camera& cam) { s.updateDensifyGrad(r, cam); })
+        .def("densifiyGs", [](SLAMGaussianModel& s, float scene_scale, int curr_iter, c10::optional<torch::Tensor> samples) {
+            return s.densifiyGs(scene_scale, curr_iter, samples);
+        }, py::arg("scene_scale"), py::arg("curr_iter"), py::arg("split_samples") = py::none())
+        .def("resetOpacities", &SLAMGaussianModel::resetOpacities)
+        .def("setDensifySeed", &SLAMGaussianModel::setDensifySeed)
+        .def("densifyStats", &SLAMGaussianModel::densifyStats)
+        .def("lastSplitSamples", &SLAMGaussianModel::lastSplitSamples)
+        .def_readwrite("densify_start_iter", &SLAMGaussianModel::densify_start_iter)
+        .def_readwrite("densify_end_iter", &SLAMGaussianModel::densify_end_iter)
+        .def_readwrite("densify_interval", &SLAMGaussianModel::densify_interval)
+        .def_readwrite("densify_grad_thres", &SLAMGaussianModel::densify_grad_thres)
+        .def_readwrite("densify_large_thres", &SLAMGaussianModel::densify_large_thres)
+        .def_readwrite("reset_opacity_interval", &SLAMGaussianModel::reset_opacity_interval)
+        .def_readwrite("prune_opacity_thres", &SLAMGaussianModel::prune_opacity_thres)
+        .def_readwrite("pause_refine_after_reset", &SLAMGaussianModel::pause_refine_after_reset)
+        .def_readonly("densify_events", &SLAMGaussianModel::densify_events)
+        .def_readonly("densify_log", &SLAMGaussianModel::densify_log)
+        .def_readonly("opacity_reset_log", &SLAMGaussianModel::opacity_reset_log)
         .def("grads", &SLAMGaussianModel::grads)
         .def("leafGrads", &SLAMGaussianModel::leafGrads)
         .def("getExposure", &SLAMGaussianModel::getExposure)
@@ -812,6 +843,11 @@ PYBIND11_MODULE(_host, m) {
         .def("gesTrainCamsWithLayers", [](SLAMPipeline& p, const std::vector<Camera>& cams, const std::vector<TensorDict>& layers, int max_iterations,
                                           int64_t seed) { return p.gesTrainCams(cams, layers, max_iterations, seed); },
              py::arg("cams"), py::arg("base_layers"), py::arg("max_iterations") = -1, py::arg("seed") = -1, py::call_guard<py::gil_scoped_release>())
+        .def("rawTrainCams", [](SLAMPipeline& p, const std::vector<Camera>& cams, int max_iterations, int64_t seed, bool densify) {
+            return p.rawTrainCams(cams, max_iterations, seed, densify);
+        }, py::arg("cams"), py::arg("max_iterations") = -1, py::arg("seed") = -1, py::arg("densify") = false,
+             py::call_guard<py::gil_scoped_release>())
+        .def("trainCams", &SLAMPipeline::trainCams, py::arg("cams"), py::arg("mode"), py::call_guard<py::gil_scoped_release>())
         .def("refineKeyframeCams", [](SLAMPipeline& p) { { py::gil_scoped_release nogil; p.flush(); } return p.refineKeyframeCams(); })
         .def("refineCacheBytes", &SLAMPipeline::refineCacheBytes, py::arg("cams"))
         .def("refineLog", [](SLAMPipeline& p) {

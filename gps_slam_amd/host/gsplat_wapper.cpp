@@ -191,10 +191,11 @@ tensor_list RasterizeToPixelsGes::backward(AutogradContext* ctx, tensor_list g) 
 tensor_list RasterizeToPixels::forward(AutogradContext* ctx, torch::Tensor means2d, torch::Tensor conics, torch::Tensor colors,
                                        torch::Tensor opacities, c10::optional<torch::Tensor> backgrounds,
                                        c10::optional<torch::Tensor> masks, int width, int height, int tile_size,
-                                       torch::Tensor isect_offsets, torch::Tensor flatten_ids, bool absgrad) {
+                                       torch::Tensor isect_offsets, torch::Tensor flatten_ids, bool absgrad, bool ordered) {
     means2d = contig_f32(means2d, "means2d"); conics = contig_f32(conics, "conics");
     colors = contig_f32(colors, "colors"); opacities = contig_f32(opacities, "opacities");
     TORCH_CHECK(means2d.size(0) == 1, "single camera (C == 1)");
+    ctx->saved_data["ordered"] = ordered;
     isect_offsets = isect_offsets.contiguous(); flatten_ids = flatten_ids.contiguous();
     if (backgrounds.has_value() && backgrounds->defined()) backgrounds = contig_f32(*backgrounds, "backgrounds");
     auto r = gsplat::rasterize_to_pixels_fwd_tensor(means2d, conics, colors, opacities, backgrounds, masks, (uint32_t)width,
@@ -217,10 +218,13 @@ tensor_list RasterizeToPixels::backward(AutogradContext* ctx, tensor_list g) {
     auto v_rc = grad_or_zeros(g[0], {1, height, width, 4}, s[0], "v_render_colors");
     auto v_ra = grad_or_zeros(g[1], {1, height, width, 1}, s[0], "v_render_alphas");
     // backgrounds = nullopt: the reference's backward never receives them (gsplat_wapper.hpp:307)
-    auto r = gsplat::rasterize_to_pixels_bwd_tensor(s[0], s[1], s[2], s[3], at::nullopt, at::nullopt, (uint32_t)width,
-                                                    (uint32_t)height, (uint32_t)tile_size, s[4], s[5], render_alphas, s[7],
-                                                    v_rc, v_ra, absgrad);
-    tensor_list out(12);
+    auto r = ctx->saved_data["ordered"].toBool()
+                 ? gsplat::rasterize_to_pixels_bwd_ordered_tensor(s[0], s[1], s[2], s[3], at::nullopt, (uint32_t)width, (uint32_t)height,
+                                                                  (uint32_t)tile_size, s[4], s[5], render_alphas, s[7], v_rc, v_ra, absgrad)
+                 : gsplat::rasterize_to_pixels_bwd_tensor(s[0], s[1], s[2], s[3], at::nullopt, at::nullopt, (uint32_t)width,
+                                                          (uint32_t)height, (uint32_t)tile_size, s[4], s[5], render_alphas, s[7],
+                                                          v_rc, v_ra, absgrad);
+    tensor_list out(13);
     out[0] = std::get<1>(r); out[1] = std::get<2>(r); out[2] = std::get<3>(r); out[3] = std::get<4>(r);
     if (ctx->needs_input_grad(4)) out[4] = (v_rc * (1.0 - render_alphas)).sum({1, 2});
     return out;

@@ -71,7 +71,7 @@ struct RasterizeToPixels : public torch::autograd::Function<RasterizeToPixels> {
                                                 c10::optional<torch::Tensor> backgrounds,
                                                 c10::optional<torch::Tensor> masks, int width, int height,
                                                 int tile_size, torch::Tensor isect_offsets, torch::Tensor flatten_ids,
-                                                bool absgrad);
+                                                bool absgrad, bool ordered = false);   // ordered: the backward without float atomics
     static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
                                                  torch::autograd::tensor_list grad_outputs);
 };

@@ -240,6 +240,42 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     return std::make_tuple(v_abs, v_means2d, v_conics, v_colors, v_opacities);
 }
 
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> rasterize_to_pixels_bwd_ordered_tensor(
+    const torch::Tensor& means2d, const torch::Tensor& conics, const torch::Tensor& colors, const torch::Tensor& opacities,
+    const at::optional<torch::Tensor>& backgrounds, const uint32_t image_width, const uint32_t image_height, const uint32_t tile_size,
+    const torch::Tensor& tile_offsets, const torch::Tensor& flatten_ids, const torch::Tensor& render_alphas,
+    const torch::Tensor& last_ids, const torch::Tensor& v_render_colors, const torch::Tensor& v_render_alphas, bool absgrad) {
+    f32_input(means2d, "means2d"); f32_input(conics, "conics"); f32_input(colors, "colors"); f32_input(opacities, "opacities");
+    f32_input(render_alphas, "render_alphas"); f32_input(v_render_colors, "v_render_colors");
+    f32_input(v_render_alphas, "v_render_alphas");
+    GPS_CHECK_INPUT(tile_offsets); GPS_CHECK_INPUT(flatten_ids); GPS_CHECK_INPUT(last_ids);
+    TORCH_CHECK(colors.size(-1) == 4, "the raw path renders rgb + depth (raw_gs_model.cpp:117)");
+    TORCH_CHECK(flatten_ids.scalar_type() == torch::kInt32, "flatten_ids must be int32");
+    torch::Tensor bg;
+    if (has(backgrounds)) { bg = *backgrounds; f32_input(bg, "backgrounds"); }
+    const int N = (int)opacities.numel();
+    const int64_t n_isects = flatten_ids.numel();
+    const auto dev = means2d.device();
+    auto counts = counts_for(n_isects, 0, dev);
+    // intersections by Gaussian, ties in ascending index: the order the second launch sums in
+    torch::Tensor order, isect_grads;
+    if (n_isects > 0) {
+        order = std::get<1>(torch::sort(flatten_ids, /*stable=*/true, 0, false)).to(torch::kInt32);
+        isect_grads = torch::empty({n_isects, 12}, f32(dev));
+    }
+    auto v_means2d = torch::empty_like(means2d), v_conics = torch::empty_like(conics);
+    auto v_colors = torch::empty_like(colors), v_opacities = torch::empty_like(opacities);
+    torch::Tensor v_abs;
+    if (absgrad) v_abs = torch::empty_like(means2d);
+    check(gps_raster_raw_bwd_ordered(N, fptr(means2d), fptr(conics), fptr(colors), fptr(opacities), bg.defined() ? fptr(bg) : nullptr,
+                                     (int)image_width, (int)image_height, (int)tile_size, iptr(tile_offsets), iptr(flatten_ids),
+                                     ptr<int64_t>(counts), n_isects, iptr(order), fptr(isect_grads), fptr(render_alphas),
+                                     iptr(last_ids), fptr(v_render_colors), fptr(v_render_alphas), absgrad ? fptr(v_abs) : nullptr,
+                                     fptr(v_means2d), fptr(v_conics), fptr(v_colors), fptr(v_opacities), current_stream()),
+          "gps_raster_raw_bwd_ordered");
+    return std::make_tuple(v_abs, v_means2d, v_conics, v_colors, v_opacities);
+}
+
 // ------------------------------------------------------------------------------------------------ ges rasterizer
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> rasterize_to_pixels_fwd_ges_tensor(
     const torch::Tensor& means2d, const torch::Tensor& conics, const torch::Tensor& colors, const torch::Tensor& opacities,

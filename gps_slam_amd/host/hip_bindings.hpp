@@ -79,6 +79,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const torch::Tensor& flatten_ids, const torch::Tensor& render_alphas, const torch::Tensor& last_ids,
     const torch::Tensor& v_render_colors, const torch::Tensor& v_render_alphas, bool absgrad);
 
+// the same with gps_raster_raw_bwd_ordered: no float atomics, two calls on the same inputs give the same bits (a stable sort of
+// flatten_ids and a per-intersection gradient buffer on top)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> rasterize_to_pixels_bwd_ordered_tensor(
+    const torch::Tensor& means2d, const torch::Tensor& conics, const torch::Tensor& colors, const torch::Tensor& opacities,
+    const at::optional<torch::Tensor>& backgrounds, const uint32_t image_width, const uint32_t image_height, const uint32_t tile_size,
+    const torch::Tensor& tile_offsets, const torch::Tensor& flatten_ids, const torch::Tensor& render_alphas,
+    const torch::Tensor& last_ids, const torch::Tensor& v_render_colors, const torch::Tensor& v_render_alphas, bool absgrad);
+
 // bindings.h:258-292 <- rasterize_to_pixels_bwd_ges.cu:164-291 (exact tile-parallel adjoint)
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> rasterize_to_pixels_bwd_ges_tensor(
     const torch::Tensor& means2d, const torch::Tensor& conics, const torch::Tensor& colors, const torch::Tensor& opacities,

@@ -324,7 +324,7 @@ TensorDict RawGaussianModel::rawForward(const Camera& cam) {
     c10::optional<torch::Tensor> bg;
     if (backgrounds.defined()) bg = backgrounds;
     auto rast = RasterizeToPixels::apply(means2d, conics, colors, torch::sigmoid(P(5)), bg, c10::nullopt, cam.width, cam.height,
-                                         tile_size, isect_offsets, isec[2], abs_grad);
+                                         tile_size, isect_offsets, isec[2], abs_grad, ordered_raw_backward);
     auto render_colors = rast[0], render_alphas = rast[1];
     const int64_t last_dim = render_colors.size(-1);
     auto rgb = render_colors.slice(-1, 0, last_dim - 1);
@@ -646,6 +646,163 @@ void RawGaussianModel::applyPendingPrunes() {
         }
     }
     pending_prunes_.clear();
+}
+
+// ------------------------------------------------------------------------------------------------ densification
+void RawGaussianModel::setDensifySeed(int64_t seed) { densify_gen_ = at::detail::createCPUGenerator((uint64_t)seed); }
+
+void RawGaussianModel::densifyStatBuffers() {
+    const int64_t cap = opt_gs_params.capacity();
+    if (grad_sum_.defined() && grad_sum_.size(0) == cap) return;
+    // (a capacity change outside densifiyGs: the rows accumulated so far move along)
+    auto grow = [&](torch::Tensor& t) {
+        auto nb = torch::zeros({cap}, f32(device));
+        if (t.defined()) { const int64_t n = std::min<int64_t>(t.size(0), cap); nb.slice(0, 0, n).copy_(t.slice(0, 0, n)); }
+        t = nb;
+    };
+    grow(grad_sum_); grow(vis_count_);
+}
+
+std::vector<torch::Tensor> RawGaussianModel::densifyStats() {
+    if (opt_gs_params.capacity() == 0) return {};
+    densifyStatBuffers();
+    const int64_t N = getGaussianNum();
+    return {grad_sum_.slice(0, 0, N), vis_count_.slice(0, 0, N)};
+}
+
+void RawGaussianModel::updateDensifyGrad(TensorDict& render_res, const Camera& cam) {
+    torch::NoGradGuard no_grad;
+    const int64_t N = getGaussianNum();
+    auto g = render_res.at("means2d").grad();
+    TORCH_CHECK(g.defined(), "updateDensifyGrad: render_res[\"means2d\"] has no gradient (retain_grad() before backward())");
+    g = g.contiguous();
+    auto radii = render_res.at("radiis").contiguous();
+    check_f32_dev(g, "means2d.grad()");
+    TORCH_CHECK(g.numel() == 2 * N && radii.numel() == N && radii.scalar_type() == torch::kInt32 && radii.is_cuda(),
+                "updateDensifyGrad: means2d.grad() [N,2] float and radiis [N] int32 of the model's ", N, " Gaussians");
+    densifyStatBuffers();
+    // (max2DSize is not kept: the reference accumulates it and reads it nowhere, raw_gs_model.cpp:608-609 is commented out)
+    check(gps_densify_accumulate((int)N, fptr(g), iptr(radii), cam.width, cam.height, fptr(grad_sum_), fptr(vis_count_),
+                                 current_stream()), "gps_densify_accumulate");
+}
+
+void RawGaussianModel::resetOpacities() {
+    torch::NoGradGuard no_grad;
+    const int64_t N = getGaussianNum();
+    if (N == 0) return;
+    applyPendingPrunes();
+    // raw_gs_model.cpp:449: clamp_max(opacities, logit(tensor(2 * prune_opacity_thres))) -- the float logit a host tensor gives
+    const float reset_opacity_target = 2 * prune_opacity_thres;
+    const float top = torch::logit(torch::tensor(reset_opacity_target)).item<float>();
+    opt_gs_params.view(5).clamp_max_(top);
+    // replaceToOptimizer: fresh (zero) moments for the replaced tensor, the optimiser's step count stays
+    if (have_opt_ && adam_cap_ == opt_gs_params.capacity()) { adam_m_[5].slice(0, 0, N).zero_(); adam_v_[5].slice(0, 0, N).zero_(); }
+    prefetched_ = PrefetchKey{};
+    if (!leaf_.empty()) setParamsRequireGrad();
+}
+
+void RawGaussianModel::stepPostBackward(TensorDict& render_res, const Camera& cam, float scene_scale, int curr_iter) {
+    torch::NoGradGuard no_grad;
+    if (curr_iter >= densify_end_iter) return;
+    updateDensifyGrad(render_res, cam);
+    if (curr_iter % densify_interval == 0 && curr_iter > densify_start_iter) {
+        std::vector<int64_t> entry = {curr_iter};
+        for (int64_t c : densifiyGs(scene_scale, curr_iter)) entry.push_back(c);
+        densify_log.push_back(entry);
+        if (grad_sum_.defined()) { grad_sum_.zero_(); vis_count_.zero_(); }   // (the reference drops the tensors: :440-442)
+    }
+    if (curr_iter % reset_opacity_interval == 0) {   // (0 % k == 0: iteration 0 resets as well, as in the reference)
+        resetOpacities();
+        opacity_reset_log.push_back(curr_iter);
+    }
+}
+
+std::vector<int64_t> RawGaussianModel::densifiyGs(float scene_scale, int curr_iter, const c10::optional<torch::Tensor>& split_samples) {
+    torch::NoGradGuard no_grad;
+    if (!(curr_iter % reset_opacity_interval >= pause_refine_after_reset)) return {};
+    RawGaussianParams& p = opt_gs_params;
+    const int64_t N = p.getGaussianNum();
+    if (N == 0) return {};
+    applyPendingPrunes();
+    densifyStatBuffers();
+    const int K = p.shK();
+    auto stream = c10::hip::getCurrentHIPStream();
+    const gps_stream s = (gps_stream)stream.stream();
+    // plan
+    auto dst_src = torch::empty({2 * N}, i32(device)), dst_sample = torch::empty({2 * N}, i32(device));
+    auto counts = torch::empty({GPS_DENSIFY_COUNTS}, i32(device));
+    auto ws = torch::empty({gps_densify_plan_workspace_bytes((int)N)}, u8(device));
+    if (!densify_host_counts_.defined())
+        densify_host_counts_ = torch::zeros({16}, torch::TensorOptions().dtype(torch::kInt32).pinned_memory(true));
+    const float inf = std::numeric_limits<float>::infinity();
+    const float split_scale = densify_large_thres * scene_scale;
+    const float prune_scale = curr_iter > reset_opacity_interval ? 0.1f * scene_scale : inf;   // pruneScaleThresh, :601-611
+    check(gps_densify_plan((int)N, fptr(grad_sum_), fptr(vis_count_), fptr(p.buffer(1)), fptr(p.buffer(5)), densify_grad_thres,
+                           split_scale, prune_opacity_thres, prune_scale, iptr(dst_src), iptr(dst_sample), 2 * N, iptr(counts),
+                           densify_host_counts_.data_ptr<int32_t>(), ws.data_ptr(), ws.numel(), s), "gps_densify_plan");
+    stream.synchronize();   // THE host synchronisation of a densification (the reference: a dozen .item() calls)
+    const int32_t* hc = densify_host_counts_.data_ptr<int32_t>();
+    const int64_t M = hc[0], n_split = hc[1], n_ss = hc[2], n_ds = hc[3], n_keep = hc[4];
+    std::vector<int64_t> out = {M, n_split, n_ss, n_ds, n_keep};
+    if (n_keep == N && M == N) return out;   // nothing cloned, split or pruned
+    // samples: one normal draw per split parent and sample, survivor or not (torch::randn({2 * nSplits, 3}), :544)
+    torch::Tensor samples;
+    if (n_split > 0) {
+        if (split_samples.has_value()) {
+            samples = split_samples->to(device, torch::kFloat32).contiguous();
+            TORCH_CHECK(samples.numel() == 2 * n_split * 3, "densifiyGs: split_samples must be [", 2 * n_split, ", 3] (2 x the ", n_split,
+                        " split parents), got ", samples.numel(), " values");
+        } else if (densify_gen_.has_value()) {
+            samples = torch::randn({2 * n_split, 3}, *densify_gen_, torch::TensorOptions().dtype(torch::kFloat32)).to(device);
+        } else {
+            samples = torch::randn({2 * n_split, 3}, f32(device));
+        }
+        last_split_samples_ = samples;
+    }
+    // destinations: the alternate parameter buffers, fresh moment buffers -- at the grown capacity when M does not fit
+    const int64_t cap = p.capacity();
+    const int64_t new_cap = M <= cap ? cap : std::max<int64_t>(2 * cap, std::max<int64_t>(1 << 19, M));
+    const bool moments = have_opt_ && adam_cap_ == cap;
+    auto like = [&](const torch::Tensor& t) {
+        std::vector<int64_t> shape = t.sizes().vec();
+        shape[0] = new_cap;
+        return torch::empty(shape, t.options());
+    };
+    std::vector<torch::Tensor> new_m(6), new_v(6);
+    const float *src[6], *sm[6], *sv[6];
+    float *dst[6], *dm[6], *dv[6];
+    for (int k = 0; k < 6; k++) {
+        if (new_cap != cap) p.alt_[k] = like(p.buf_[k]);
+        src[k] = fptr(p.buf_[k]); dst[k] = fptr(p.alt_[k]);
+        if (moments) {
+            new_m[k] = like(adam_m_[k]); new_v[k] = like(adam_v_[k]);
+            sm[k] = fptr(adam_m_[k]); dm[k] = fptr(new_m[k]); sv[k] = fptr(adam_v_[k]); dv[k] = fptr(new_v[k]);
+        }
+    }
+    check(gps_densify_apply((int)N, K, (int)M, (int)n_split, (int)n_ss, (int)n_ds, (int)n_keep, iptr(dst_src), iptr(dst_sample),
+                            fptr(samples), src, dst, moments ? sm : nullptr, moments ? dm : nullptr, moments ? sv : nullptr,
+                            moments ? dv : nullptr, s), "gps_densify_apply");
+    for (int k = 0; k < 6; k++) {
+        std::swap(p.buf_[k], p.alt_[k]);
+        if (new_cap != cap) p.alt_[k] = like(p.buf_[k]);   // (stream ordered: the old buffer is released behind the apply)
+        if (moments) { adam_m_[k] = new_m[k]; adam_v_[k] = new_v[k]; }
+        if (new_cap != cap && have_opt_) adam_g_[k] = torch::zeros_like(p.buf_[k]);
+    }
+    if (new_cap != cap) {
+        p.cap_ = new_cap;
+        if (have_opt_) adam_cap_ = new_cap;   // (stepStruct() sees the new capacity and rebuilds the step buffers)
+        grad_sum_ = torch::Tensor(); vis_count_ = torch::Tensor();
+        densifyStatBuffers();
+    } else {
+        grad_sum_.zero_(); vis_count_.zero_();   // the statistics belonged to the old rows (the reference drops them: :440-442)
+    }
+    p.N_ = M;
+    p.version_++;   // a forward run ahead for the old rows is void
+    p.keep_ids32_ = torch::Tensor(); p.keep_idx_ = torch::Tensor();
+    prefetched_ = PrefetchKey{};
+    densify_events++;
+    if (!leaf_.empty()) setParamsRequireGrad();
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------ addGaussians

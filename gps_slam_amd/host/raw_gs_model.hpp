@@ -88,6 +88,37 @@ public:
     int64_t pruneKeep(const torch::Tensor& keepMask);   // prunePoints(~keepMask); returns the number of Gaussians kept
     void setParamsRequireGrad();
 
+    // ---- densification (raw_gs_model.cpp:419-633), driven by SLAMPipeline::rawTrainCams ----
+    // stepPostBackward: the reference's control flow.  While curr_iter < densify_end_iter: the statistics of updateDensifyGrad
+    // from render_res["means2d"].grad() (retain_grad() before backward) and render_res["radiis"] in ONE launch
+    // (gps_densify_accumulate); densifiyGs + cleared statistics when curr_iter % densify_interval == 0 && curr_iter >
+    // densify_start_iter; the opacity reset when curr_iter % reset_opacity_interval == 0 -- at iteration 0 too (0 % k == 0), as
+    // the reference has it: logits clamped to at most logit(2 prune_opacity_thres), the opacity moments zeroed, the step count kept.
+    void stepPostBackward(TensorDict& render_res, const Camera& cam, float scene_scale, int curr_iter);
+    void updateDensifyGrad(TensorDict& render_res, const Camera& cam);
+    // clone / split / prune as ONE plan (gps_densify_plan), ONE stream synchronise for its five counts and ONE out-of-place pass
+    // over parameters and Adam moments (gps_densify_apply) into the alternate buffers, which then become the model: see
+    // include/gps_slam_hip.h for the layout (the reference's cat + order-preserving prune).  Grows every capacity-sized buffer
+    // when the new count exceeds the capacity (the parameters' own policy: at least double, at least 2^19 rows); contents and the
+    // step count survive.  split_samples [2 n_split, 3]: the normal draws (the reference: torch::randn); without them they come
+    // from the generator of setDensifySeed(), or the default one.  Nothing happens while curr_iter % reset_opacity_interval <
+    // pause_refine_after_reset (raw_gs_model.cpp:513).  Returns the counts {M, n_split, n_split_surviving, n_dup_surviving, n_keep}
+    // (empty when paused or when the model is empty).
+    std::vector<int64_t> densifiyGs(float scene_scale, int curr_iter, const c10::optional<torch::Tensor>& split_samples = c10::nullopt);
+    void resetOpacities();
+    void setDensifySeed(int64_t seed);   // a host generator for the split samples: the same on every device
+    // the statistics as [:N] views {grad_sum, vis_count} (zero until something is accumulated); the caller may write them
+    std::vector<torch::Tensor> densifyStats();
+    torch::Tensor lastSplitSamples() const { return last_split_samples_; }   // the draws of the last densifiyGs that split (undefined: none yet)
+    int densify_start_iter = 500, densify_end_iter = 6000, densify_interval = 100, reset_opacity_interval = 3000;
+    float densify_grad_thres = 0.0002f, densify_large_thres = 0.01f, prune_opacity_thres = 0.005f;
+    int pause_refine_after_reset = 0;    // raw_gs_model.h: a member, no key
+    int64_t densify_events = 0;          // densifiyGs calls that changed the model
+    // what stepPostBackward did, for callers that want to see the schedule: {curr_iter, M, n_split, n_split_surviving,
+    // n_dup_surviving, n_keep} per densifiyGs it ran (paused calls: {curr_iter}), and the iterations of its opacity resets
+    std::vector<std::vector<int64_t>> densify_log;
+    std::vector<int> opacity_reset_log;
+
     RawGaussianParams& getGaussianParms() { return opt_gs_params; }
     int getMaxSH() const { return maxSH; }
     torch::Tensor getMeans() { return opt_gs_params.getMeans(); }
@@ -160,6 +191,9 @@ public:
     double exposure_lr = 0.003;
     std::string render_method = "ges";
     bool abs_grad = false;       // raw_gs_model.h:293
+    // rawForward's rasterizer backward without float atomics (gps_raster_raw_bwd_ordered): the same inputs give the same bits, at
+    // the price of a sort and a second pass.  SLAMPipeline::rawTrainCams switches it on: two runs with one seed end bit-identical
+    bool ordered_raw_backward = false;
     torch::Tensor backgrounds;   // raw_gs_model.h:295 ([1,4] device tensor; undefined = none)
 
     // implementation detail, public for the autograd node
@@ -218,6 +252,11 @@ protected:
     struct PendingPrune { torch::Tensor keep; int64_t n_before; };
     std::vector<PendingPrune> pending_prunes_;  // prunePoints' Adam-state compactions not carried out yet
     void applyPendingPrunes();
+    torch::Tensor grad_sum_, vis_count_;   // densification statistics, capacity sized (zero = cleared)
+    torch::Tensor densify_host_counts_;    // pinned words gps_densify_plan reports its counts in
+    c10::optional<at::Generator> densify_gen_;
+    torch::Tensor last_split_samples_;
+    void densifyStatBuffers();
     torch::Tensor host_count_;         // pinned word the mask compaction reports its count in (addGaussians)
     torch::Tensor host_subset_;        // pinned staging buffer of the sampled subset
 };
@@ -255,10 +294,18 @@ void RawGaussianModel::configFields(V& v, int64_t& capacity) {
     v.b("fuse_sh_rest_adam", fuse_sh_rest_adam, gpsh::kOptional);
     v.b("strip_backward", strip_backward, gpsh::kOptional);
     v.i64("capacity", capacity, gpsh::kOptional);
-    // in every shipped file, read by nothing the SLAM loop runs (densification: DESIGN.md section 8)
-    for (const char* k : {"means_lr_final", "densify_start_iter", "densify_end_iter", "densify_interval", "densify_grad_thres",
-                          "densify_large_thres", "split_screen_size", "reset_opacity_interval", "prune_opacity_thres"})
-        v.ignored(k);
+    // densification (stepPostBackward / densifiyGs read them from the node when they run, raw_gs_model.cpp:423-427, :505-510: a
+    // file without them loads, so they are optional here)
+    v.i("densify_start_iter", densify_start_iter, gpsh::kOptional);
+    v.i("densify_end_iter", densify_end_iter, gpsh::kOptional);
+    v.i("densify_interval", densify_interval, gpsh::kOptional);
+    v.f("densify_grad_thres", densify_grad_thres, gpsh::kOptional);
+    v.f("densify_large_thres", densify_large_thres, gpsh::kOptional);
+    v.i("reset_opacity_interval", reset_opacity_interval, gpsh::kOptional);
+    v.f("prune_opacity_thres", prune_opacity_thres, gpsh::kOptional);
+    // in every shipped file, used by nothing: the scheduler's final rate is 0.01 x the start (raw_gs_model.cpp:673), and
+    // densifiyGs reads split_screen_size into a local it never uses (:508)
+    for (const char* k : {"means_lr_final", "split_screen_size"}) v.ignored(k);
 }
 
 template <class N>

@@ -689,6 +689,59 @@ int SLAMPipeline::refineLoop(const std::vector<Camera>& cams, std::vector<Tensor
     return curr_iter - first;
 }
 
+// ------------------------------------------------------------------ rawTrainCams (src/pipeline.cpp:155-226)
+int SLAMPipeline::rawTrainCams(const std::vector<Camera>& cams, int max_iters, int64_t seed, bool densify) {
+    flush();
+    TORCH_CHECK(model != nullptr, "rawTrainCams: no model (setModel first)");
+    TORCH_CHECK(model->getRenderMethod() == "raw", "rawTrainCams: render_method must be 'raw', got '", model->getRenderMethod(), "'");   // :157
+    TORCH_CHECK(!cams.empty(), "rawTrainCams: no cameras");
+    if (max_iters < 0) max_iters = max_iterations;
+    if (seed < 0) seed = refine_seed;
+    TORCH_CHECK(selected_cam_idx >= -1 && selected_cam_idx < (int)cams.size(), "rawTrainCams: selected_cam_idx ", selected_cam_idx, " with ",
+                cams.size(), " cameras");
+    if (curr_iter >= max_iters || model->getGaussianNum() == 0) return 0;
+    std::vector<Camera> dev = refineDeviceCams(cams, device);
+    model->initOptimizers(max_iters, scene_scale);   // ONE optimiser state for the whole call, with the means' scheduler (:176)
+    model->setDensifySeed(seed);                     // the split samples: a second stream of the same seed
+    // one seed, one result: the rasterizer's backward with a reduction of fixed order (the atomic one differs run to run in the last
+    // bits, and the differences grow over thousands of iterations and densifications)
+    struct Ordered {
+        SLAMGaussianModel* m; bool was;
+        explicit Ordered(SLAMGaussianModel* m) : m(m), was(m->ordered_raw_backward) { m->ordered_raw_backward = true; }
+        ~Ordered() { m->ordered_raw_backward = was; }
+    } ordered(model);
+    gpsh::RandomSelector<Camera> loader(dev, (uint64_t)seed);
+    Config wc;
+    wc.num["ssim_weight"] = ssim_weight; wc.num["depth_weight"] = depth_weight;
+    const int first = curr_iter;
+    for (; curr_iter < max_iters; curr_iter++) {
+        const size_t idx = selected_cam_idx == -1 ? loader.getNext().originalIndex : (size_t)selected_cam_idx;
+        const Camera& cam = dev[idx];
+        model->updateSH(curr_iter);
+        TensorDict render_res = model->forward(cam);
+        if (densify) render_res["means2d"].retain_grad();
+        TensorDict loss = model->computeLoss(render_res, cam, wc);
+        loss["total"].backward();
+        model->optimizersStep();
+        model->optimizersZeroGrad();
+        if (densify) model->stepPostBackward(render_res, cam, scene_scale, curr_iter);
+        model->schedulersStep();
+        stats.opt_iters++;
+        const bool last = curr_iter + 1 == max_iters;
+        if (last || (log_iter > 0 && (curr_iter + 1) % log_iter == 0))   // (blocks: the loop's only read of the loss)
+            refine_log.push_back({curr_iter, loss["total"].item<float>()});
+        if (model->getGaussianNum() == 0) { curr_iter++; break; }   // everything pruned: nothing left to optimise
+    }
+    return curr_iter - first;
+}
+
+int SLAMPipeline::trainCams(const std::vector<Camera>& cams, const std::string& mode) {
+    TORCH_CHECK(mode == "raw" || mode == "ges", "trainCams: mode 'raw' or 'ges', got '", mode, "'");
+    TORCH_CHECK(model != nullptr, "trainCams: no model (setModel first)");
+    TORCH_CHECK(model->getRenderMethod() == mode, "trainCams: render_method must be '", mode, "', got '", model->getRenderMethod(), "'");
+    return mode == "raw" ? rawTrainCams(cams) : gesTrainCams(cams);
+}
+
 // ------------------------------------------------------------------ removeRedundantGs :564-586
 void SLAMPipeline::removeRedundantGs() {
     torch::NoGradGuard no_grad;

@@ -137,6 +137,15 @@ public:
     int gesTrainCams(const std::vector<Camera>& cams, int max_iterations = -1, int64_t seed = -1);
     int gesTrainCams(const std::vector<Camera>& cams, const std::vector<TensorDict>& base_layers, int max_iterations = -1, int64_t seed = -1);
     int64_t refineCacheBytes(const std::vector<Camera>& cams) const;   // what gesTrainCams holds on the device for these cameras
+    // Pipeline::rawTrainCams (src/pipeline.cpp:155-226), the classic 3DGS trainer over posed images: no TSDF layer, no engine.
+    // render_method must be "raw".  ONE initOptimizers(max_iterations, scene_scale); per iteration the camera from the seeded
+    // RandomSelector (or cams[selected_cam_idx]), updateSH, forward, computeLoss, backward, optimizersStep, optimizersZeroGrad,
+    // with `densify` retain_grad() on means2d and stepPostBackward (RawGaussianModel: clone / split / prune / opacity reset, its
+    // split samples from a generator of the same seed), schedulersStep.  The loss is read every log_iter iterations and at the
+    // last one into refine_log.  The reference's switch is PIPE.enable_densify, which the SLAM configuration refuses: here it is
+    // the argument.  curr_iter, max_iterations < 0, seed < 0: as gesTrainCams.  Returns the number of iterations run.
+    int rawTrainCams(const std::vector<Camera>& cams, int max_iterations = -1, int64_t seed = -1, bool densify = false);
+    int trainCams(const std::vector<Camera>& cams, const std::string& mode);   // "raw" | "ges" (src/pipeline.cpp trainCams)
     int curr_iter = 0;
     struct RefineLogEntry { int iter; float loss; };
     std::vector<RefineLogEntry> refine_log;

@@ -289,6 +289,20 @@ GPS_API int gps_raster_raw_bwd(int N, const float *means2d, const float *conics,
                                const float *v_render_alphas, float *v_means2d_abs, float *v_means2d, float *v_conics,
                                float *v_colors, float *v_opacities, gps_stream stream);
 
+/* The same gradients with a reduction of FIXED order, so that two calls on the same inputs give the same bits (gps_raster_raw_bwd
+ * sums with float atomics, in the order the waves arrive): the tile kernel writes one row of 12 totals per intersection into
+ * isect_grads[n_isects, 12] (the four waves of a tile summed in wave order), a second launch sums every Gaussian's rows in
+ * ascending intersection order.  n_isects: the exact length of flatten_ids (counts[0] holds it too); order[n_isects]: the
+ * intersection indices sorted by Gaussian id, ties ascending (a stable sort of flatten_ids).  Every output element is written.
+ * The offline trainer uses it (SLAMPipeline::rawTrainCams); it is slower than the atomic version by the sort and the second pass. */
+GPS_API int gps_raster_raw_bwd_ordered(int N, const float *means2d, const float *conics, const float *colors,
+                                       const float *opacities, const float *backgrounds, int width, int height, int tile_size,
+                                       const int32_t *tile_offsets, const int32_t *flatten_ids, const int64_t *counts,
+                                       int64_t n_isects, const int32_t *order, float *isect_grads, const float *render_alphas,
+                                       const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
+                                       float *v_means2d_abs, float *v_means2d, float *v_conics, float *v_colors,
+                                       float *v_opacities, gps_stream stream);
+
 /* ------------------------------------------------------------------ */
 /* Splat: compose + L1 loss (fused replacement of libtorch glue)       */
 /* ------------------------------------------------------------------ */
@@ -615,6 +629,50 @@ GPS_API int gps_prune_mask(int N, const float *log_scales, const float *opac_log
  * dsts must not alias srcs. */
 GPS_API int gps_gather_rows(int m, const int32_t *ids, int n_tensors, const float *const *srcs, float *const *dsts,
                             const int32_t *row_floats, gps_stream stream);
+
+/* ---- densification of the classic 3DGS trainer (RawGaussianModel::updateDensifyGrad / densifiyGs, src/raw_gs_model.cpp:459-633) ----
+ *
+ * gps_densify_accumulate: for every row with radii[i] > 0
+ *     grad_sum[i] += |(v_means2d[i].x * width / 2, v_means2d[i].y * height / 2)|_2,   vis_count[i] += 1
+ * (v_means2d [N,2] float, 8-byte aligned; radii [N] int32; both statistics [N] float).  Other rows are not touched.  One launch.
+ *
+ * gps_densify_plan: the classes of densifiyGs per row
+ *     high = grad_sum / max(vis_count, 1) > grad_thres,  large = max(exp(log_scales)) > split_scale,
+ *     clone = high & !large,  split = high & large,
+ *     pruned = sigmoid(opac_logit) < prune_opac  |  max(exp(log_scales)) > prune_scale  |  split
+ * with the prune criteria applied to the new rows too (a clone carries its parent's values; a split child the parent's opacity
+ * and log(exp(s) / 1.6), whose exp is tested).  prune_scale = +inf switches the scale criterion off.  Writes the destination
+ * table of the new model in the reference's order (cat {originals, children, clones}, then an order-preserving prune):
+ *     d in [0, n_keep)                                    kept originals, ascending row      dst_src[d] = row
+ *     d = n_keep + s * n_split_surviving + r_surv(p)      sample s in {0, 1} of parent p     dst_src[d] = p,
+ *                                                                                            dst_sample[d] = s * n_split + r_all(p)
+ *     d = n_keep + 2 * n_split_surviving + r              surviving clones, ascending parent dst_src[d] = parent
+ * (r_surv / r_all: p's rank among the surviving / all split parents) and counts[GPS_DENSIFY_COUNTS] =
+ * {M, n_split, n_split_surviving, n_dup_surviving, n_keep} to device memory and, if host_counts != NULL (pinned, device-visible),
+ * to the host.  dst_src / dst_sample: dst_capacity >= 2 N ints each (M <= 2 N).  Two launches over GPS_DENSIFY_PLAN_BLOCK-row
+ * blocks, no host synchronisation.  GPS_ERR_CAPACITY for a workspace or a table that is too small.  N == 0 launches nothing:
+ * host_counts is zeroed by the call itself and the device words are left as they are.
+ *
+ * gps_densify_apply: writes the M rows of the new model OUT OF PLACE from the table: parameters (means[.,3], log_scales[.,3],
+ * quats[.,4], sh_dc[.,3], sh_rest[.,K-1,3], opac_logit[.,1]; arrays of six device pointers in HOST memory; the sh_rest entries may
+ * be NULL for K == 1) and, unless all four moment arrays are NULL, the Adam moments of the same shapes.  Kept originals: bit copies
+ * of parameters and moments.  Children: mean = R(q / |q|) (exp(s) * z) + mean_p with z = samples[dst_sample[d]] (samples
+ * [2 n_split, 3]: the reference draws for every split parent), log_scale = log(exp(s_p) / 1.6), everything else a bit copy, zero
+ * moments.  Clones: bit copies, zero moments.  The counts are the plan's, read by the host.  GPS_ERR_ARG before any launch for
+ * inconsistent counts, samples == NULL with n_split > 0, a NULL or aliased tensor.  M == 0 launches nothing. */
+#define GPS_DENSIFY_PLAN_BLOCK 256
+#define GPS_DENSIFY_COUNTS 5
+GPS_API int gps_densify_accumulate(int N, const float *v_means2d, const int32_t *radii, int width, int height, float *grad_sum,
+                                   float *vis_count, gps_stream stream);
+GPS_API int64_t gps_densify_plan_workspace_bytes(int N);
+GPS_API int gps_densify_plan(int N, const float *grad_sum, const float *vis_count, const float *log_scales, const float *opac_logit,
+                             float grad_thres, float split_scale, float prune_opac, float prune_scale, int32_t *dst_src,
+                             int32_t *dst_sample, int64_t dst_capacity, int32_t *counts, int32_t *host_counts, void *workspace,
+                             int64_t workspace_bytes, gps_stream stream);
+GPS_API int gps_densify_apply(int N, int K, int M, int n_split, int n_split_surviving, int n_dup_surviving, int n_keep,
+                              const int32_t *dst_src, const int32_t *dst_sample, const float *samples,
+                              const float *const *src_params, float *const *dst_params, const float *const *src_m,
+                              float *const *dst_m, const float *const *src_v, float *const *dst_v, gps_stream stream);
 
 /* replaces computeNormalMap (src/tensor_math.cpp:278-300 + featureGradient :217-248): vertex_map[H,W,3] ->
  * normal_map[H,W,3] (Sobel, replicate padding, cross(dy,dx) normalised, 0 where vertex z <= 0). */
