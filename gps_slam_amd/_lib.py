@@ -41,6 +41,20 @@ class TrackState(C.Structure):
                 ("frames_processed", i32), ("diag", f32 * 16), ("host_mailbox", vp), ("mail_seq", i32), ("scratch_epoch", i32), ("dev_arg_line", vp), ("mailbox_bytes", i32), ("n_valid_max", i32)]
 
 
+class DepthCalib(C.Structure):
+    """gps_depth_calib: type (DEPTH_CALIB_KINECT / DEPTH_CALIB_AFFINE), a, b"""
+    _fields_ = [("type", i32), ("a", f32), ("b", f32)]
+
+
+DEPTH_CALIB_KINECT, DEPTH_CALIB_AFFINE = 0, 1
+
+
+class ColourCamera(C.Structure):
+    """gps_colour_camera: a colour camera of its own (size, intrinsics, calib_inv in ORUtils layout, device image)"""
+    _fields_ = [("width", i32), ("height", i32), ("fx", f32), ("fy", f32), ("cx", f32), ("cy", f32), ("depth_to_rgb", f32 * 16),
+                ("rgb", vp)]
+
+
 class SplatStep(C.Structure):
     """gps_splat_step (include/gps_slam_hip.h)"""
     _fields_ = ([(n, i32) for n in ("N", "K", "sh_degree", "width", "height", "max_gs_radii")] +
@@ -164,6 +178,12 @@ PROTOTYPES = {
     "gps_tsdf_get_image": (i32, [C.POINTER(TsdfState), vp, vp, i32, vp, vp]),
     "gps_tsdf_filter_scratch_bytes": (i64, [i32, i32]),
     "gps_tsdf_convert_filter_depth": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
+    "gps_tsdf_convert_depth_calib": (i32, [C.POINTER(TsdfState), vp, C.POINTER(DepthCalib), vp]),
+    "gps_tsdf_convert_filter_depth_calib": (i32, [C.POINTER(TsdfState), vp, C.POINTER(DepthCalib), vp, vp]),
+    "gps_rgbd_m_rgb": (i32, [vp, vp, vp]),
+    "gps_tsdf_integrate_rgb": (i32, [C.POINTER(TsdfState), vp, C.POINTER(ColourCamera), vp]),
+    "gps_tsdf_frame_map_rgb": (i32, [C.POINTER(TsdfState), C.POINTER(TrackState), i32, i32, vp, i32, C.POINTER(ColourCamera), vp]),
+    "gps_tsdf_register_colour": (i32, [C.POINTER(TsdfState), C.POINTER(ColourCamera), vp, vp]),
     "gps_tsdf_convert_depth": (i32, [C.POINTER(TsdfState), vp, vp]),
     "gps_tsdf_allocate": (i32, [C.POINTER(TsdfState), vp, vp, vp]),
     "gps_tsdf_integrate": (i32, [C.POINTER(TsdfState), vp, vp]),

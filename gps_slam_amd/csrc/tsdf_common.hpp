@@ -113,6 +113,16 @@ static inline bool state_valid(const gps_tsdf_state& s) {
            s.icp_normals && s.fv_visible_ids && s.fv_minmax && s.fv_raycast && s.fv_colour;
 }
 
+// the calibration arguments (gps_depth_calib, gps_colour_camera): checked before any launch
+static inline bool depth_calib_valid(const gps_depth_calib& c) {
+    if (c.type != GPS_DEPTH_CALIB_KINECT && c.type != GPS_DEPTH_CALIB_AFFINE) return false;
+    // (ITMDisparityCalib::SetFrom turns "both zero" into the standard calibration, and so do the host layers; here it is refused)
+    return !(c.type == GPS_DEPTH_CALIB_KINECT && c.a == 0.0f && c.b == 0.0f);
+}
+static inline bool colour_camera_valid(const gps_colour_camera& c) {
+    return c.width > 0 && c.height > 0 && c.rgb != nullptr && (reinterpret_cast<uintptr_t>(c.rgb) & 3) == 0;
+}
+
 // r = M * (x,y,z,w), xyz only; ((m0*x + m4*y) + m8*z) + m12*w  (ORUtils/Matrix.h:130-137)
 __device__ __forceinline__ void mul_point(const Mat4& M, float x, float y, float z, float w, float& rx, float& ry,
                                           float& rz) {

@@ -284,6 +284,24 @@ int gps_tsdf_frame_map_fwd(const gps_tsdf_state* s, gps_track_state* ts, int fus
     return GPS_OK;
 }
 
+int gps_tsdf_frame_map_rgb(const gps_tsdf_state* s, gps_track_state* ts, int fuse, int reset_visible, void* fwd_block,
+                           int use_approximate_raycast, const gps_colour_camera* cam, gps_stream stream) {
+    if (cam == nullptr) return gps_tsdf_frame_map_fwd(s, ts, fuse, reset_visible, fwd_block, use_approximate_raycast, stream);
+    GPS_REQUIRE(s && ts);
+    GPS_REQUIRE(gpst::colour_camera_valid(*cam));
+    int r;
+    const double t1 = wall_ms();
+    if (fuse) {
+        if ((r = gps_tsdf_allocate(s, ts->pose_M, ts->pose_invM, stream)) != GPS_OK) return r;
+        if ((r = gps_tsdf_integrate_rgb(s, ts->pose_M, cam, stream)) != GPS_OK) return r;
+    } else {
+        if ((r = gps_tsdf_update_visible_list(s, ts->pose_M, ts->pose_invM, reset_visible, stream)) != GPS_OK) return r;
+    }
+    if ((r = gps_tsdf_prepare(s, ts, fwd_block, use_approximate_raycast, stream)) != GPS_OK) return r;
+    ts->diag[15] = (float)(wall_ms() - t1);
+    return GPS_OK;
+}
+
 int gps_tsdf_process_frame_fwd(const gps_tsdf_state* s, const int16_t* depth_mm, const float* M, const float* invM,
                                gps_track_state* ts, void* fwd_block, int use_approximate_raycast, gps_stream stream) {
     GPS_REQUIRE(s && depth_mm && M && invM && ts);

@@ -77,6 +77,25 @@ __global__ __launch_bounds__(256) void convert_depth_kernel(int P, const int16_t
     out[i] = d <= 0 ? -1.0f : (float)d * (1.0f / 1000.0f) + 0.0f;
 }
 
+// UpdateView's switch on the disparity calibration (ITMViewBuilder_CPU.cpp:41-48): convertDepthAffineToFloat(a, b) or
+// convertDisparityToDepth (ITMViewBuilder_Shared.h:8-36), in the reference's operation order -- a multiply then an add;
+// ((8 * b) * fx_d) / t with an IEEE division (this file is compiled with -ffp-contract=off)
+__global__ __launch_bounds__(256) void convert_depth_calib_kernel(int P, const int16_t* __restrict__ in, float* __restrict__ out, int type,
+                                                                  float a, float b, float fx_d) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const int16_t d = in[i];
+    if (type == GPS_DEPTH_CALIB_AFFINE) {
+        out[i] = d <= 0 ? -1.0f : (float)d * a + b;
+    } else {
+        const float t = a - (float)d;
+        float depth;
+        if (t == 0) depth = 0.0f;
+        else depth = 8.0f * b * fx_d / t;
+        out[i] = (depth > 0) ? depth : -1.0f;
+    }
+}
+
 // ---------------------------------------------------------------- allocation requests
 // Steps along the truncation band of one depth pixel (Shared.h:207-323).  The geometry is
 // recomputed by the allocation sweep from (loc, step) via the same function, so both see the
@@ -379,8 +398,22 @@ __device__ __forceinline__ bool project_voxel(const TsdfState& s, const Mat4& M,
     return !((ix < 1) || (ix > W - 2) || (iy < 1) || (iy > H - 2));
 }
 
-template <bool FAST_DIV>
-__global__ __launch_bounds__(256) void integrate_kernel(TsdfState s, Mat4 M, gps::LaunchStamp stamp) {
+// A colour camera of its own (RGB_CAM; gps_tsdf_integrate_rgb): phase 2 projects the voxel with M_rgb = calib_inv * M_d and the
+// colour intrinsics into an image of the colour camera's size, as computeUpdatedVoxelColorInfo does (Shared.h:106-140).  Without
+// it the kernel has the argument list it always had: the camera is a parameter pack, empty (the one-camera kernel) or one
+// ColourCam (an empty struct in its place would still take a slot of the argument block and move the stamp by 8 bytes).
+struct ColourCam {
+    Mat4 M;                 // M_rgb
+    float fx, fy, cx, cy;   // projParams_rgb
+    int W, H;
+    const uchar4* rgb;
+};
+__device__ __forceinline__ const ColourCam& only(const ColourCam& c) { return c; }
+
+template <bool FAST_DIV, typename... CAM>
+__global__ __launch_bounds__(256) void integrate_kernel(TsdfState s, Mat4 M, CAM... cam_pack, gps::LaunchStamp stamp) {
+    constexpr bool RGB_CAM = sizeof...(CAM) == 1;
+    static_assert(sizeof...(CAM) <= 1, "no camera, or one ColourCam");
     gps::StampScope timed(stamp);
     GPS_FRAME_PRIO();
     __shared__ uint16_t queue[4][BLK3];  // per wave: (slice << 6 | lane) of the voxels that take the colour update
@@ -395,7 +428,10 @@ __global__ __launch_bounds__(256) void integrate_kernel(TsdfState s, Mat4 M, gps
     const float mu = s.mu;
     const float inv_mu = 1.0f / mu;                       // RN(1/mu), RN(1/255), RN(1/32767) for div_known
     const float inv_255 = 1.0f / 255.0f, inv_32767 = 1.0f / 32767.0f;
-    const uchar4* img = reinterpret_cast<const uchar4*>(s.rgb);
+    const uchar4* img;
+    int Wc;   // the colour image's row length
+    if constexpr (RGB_CAM) { img = only(cam_pack...).rgb; Wc = only(cam_pack...).W; }
+    else { img = reinterpret_cast<const uchar4*>(s.rgb); Wc = W; }
     // the entry of the wave's next block and the list word of the one after it are fetched under the current block's loads
     // (clamped indices: the loads stay unconditional)
     HashEntry he_next = {};
@@ -487,16 +523,29 @@ __global__ __launch_bounds__(256) void integrate_kernel(TsdfState s, Mat4 M, gps
             const float vy = (float)(he.y * BLK + (l2 >> 3)) * s.voxel_size;
             const float vz = (float)(he.z * BLK + lz) * s.voxel_size;
             float cz, ix, iy;
-            project_voxel<FAST_DIV>(s, M, vx, vy, vz, W, H, cz, ix, iy);  // passed in phase 1: same operations, same values
+            if constexpr (RGB_CAM) {
+                // pt_camera = M_rgb * pt_model, plain IEEE divisions, the colour image's own bounds; outside: clr and w_color stay.
+                // The reference does not look at pt_camera.z: a negative z is reproduced as it computes it; a NaN coordinate
+                // (0 / 0) passes its four comparisons into a read outside the image -- here it is dropped
+                const ColourCam& cam = only(cam_pack...);
+                float cx, cy;
+                mul_point(cam.M, vx, vy, vz, 1.0f, cx, cy, cz);
+                ix = cam.fx * cx / cz + cam.cx;
+                iy = cam.fy * cy / cz + cam.cy;
+                if (!(ix == ix) || !(iy == iy)) continue;
+                if ((ix < 1) || (ix > cam.W - 2) || (iy < 1) || (iy > cam.H - 2)) continue;
+            } else {
+                // rgb camera == depth camera (trafo_rgb_to_depth is identity, InfiniTAM_tools.cpp:6-10), so the colour
+                // projection repeats the depth projection's rounding sequence exactly
+                project_voxel<FAST_DIV>(s, M, vx, vy, vz, W, H, cz, ix, iy);  // passed in phase 1: same operations, same values
+            }
             uint64_t raw = *slot;
-            // colour: rgb camera == depth camera (trafo_rgb_to_depth is identity, InfiniTAM_tools.cpp:6-10), so the
-            // colour projection repeats the depth projection's rounding sequence exactly
             const int px = (int)floorf(ix), py = (int)floorf(iy);
             const float dx = ix - (float)px, dy = iy - (float)py;
-            // the four taps go out together (1 <= ix <= W-2: all in the image); the reference reads b, c, d only when their
+            // the four taps go out together (1 <= ix <= W-2 of the colour image: all in the image); the reference reads b, c, d only when their
             // weight is non-zero and uses 0 otherwise
-            const uchar4 a = img[px + py * W];
-            uchar4 b = img[(px + 1) + py * W], c = img[px + (py + 1) * W], d = img[(px + 1) + (py + 1) * W];
+            const uchar4 a = img[px + py * Wc];
+            uchar4 b = img[(px + 1) + py * Wc], c = img[px + (py + 1) * Wc], d = img[(px + 1) + (py + 1) * Wc];
             const uchar4 zero4 = make_uchar4(0, 0, 0, 0);
             if (!(dx != 0)) b = zero4;
             if (!(dy != 0)) c = zero4;
@@ -562,6 +611,18 @@ int gps_tsdf_convert_depth(const gps_tsdf_state* sp, const int16_t* depth_mm, gp
     GPS_REQUIRE(state_valid(*sp));
     const int P = sp->width * sp->height;
     convert_depth_kernel<<<gps_div_up(P, 256), 256, 0, (hipStream_t)stream>>>(P, depth_mm, sp->depth);
+    GPS_LAUNCH_CHECK();
+    return GPS_OK;
+}
+
+int gps_tsdf_convert_depth_calib(const gps_tsdf_state* sp, const int16_t* raw, const gps_depth_calib* calib, gps_stream stream) {
+    GPS_ENTER();
+    GPS_REQUIRE(sp != nullptr && raw != nullptr && calib != nullptr);
+    GPS_REQUIRE(sp->width > 0 && sp->height > 0 && sp->depth != nullptr);
+    GPS_REQUIRE((reinterpret_cast<uintptr_t>(raw) & 1) == 0 && (reinterpret_cast<uintptr_t>(sp->depth) & 3) == 0);
+    GPS_REQUIRE(depth_calib_valid(*calib));
+    const int P = sp->width * sp->height;
+    convert_depth_calib_kernel<<<gps_div_up(P, 256), 256, 0, (hipStream_t)stream>>>(P, raw, sp->depth, calib->type, calib->a, calib->b, sp->fx);
     GPS_LAUNCH_CHECK();
     return GPS_OK;
 }
@@ -647,6 +708,42 @@ int gps_tsdf_integrate(const gps_tsdf_state* sp, const float* M, gps_stream stre
 #endif
     if (div_known_safe(s.mu)) gps::launch_kernel(gps::TK_INTEGRATE, 0, integrate_kernel<true>, dim3(GPS_INTEGRATE_WGS), dim3(256), 0, (hipStream_t)stream, s, load_mat(M));
     else gps::launch_kernel(gps::TK_INTEGRATE, 0, integrate_kernel<false>, dim3(GPS_INTEGRATE_WGS), dim3(256), 0, (hipStream_t)stream, s, load_mat(M));
+    GPS_LAUNCH_CHECK();
+    return GPS_OK;
+}
+
+// M_rgb = trafo_rgb_to_depth.calib_inv * M_d (CPU.tpp:47-48): ORUtils' Matrix4 * Matrix4 (Matrix.h:117-123), every element a sum
+// that starts at 0 and adds lhs(k, y) * rhs(x, k) for k = 0..3, in float on the host
+int gps_rgbd_m_rgb(const float* depth_to_rgb, const float* M_d, float* M_rgb) {
+    if (!depth_to_rgb || !M_d || !M_rgb) return GPS_ERR_ARG;
+    float r[16];
+    for (int x = 0; x < 4; x++)
+        for (int y = 0; y < 4; y++) {
+            volatile float acc = 0.0f;   // (volatile: the host compiler neither fuses nor reorders the four steps)
+            for (int k = 0; k < 4; k++) {
+                volatile float p = depth_to_rgb[k * 4 + y] * M_d[x * 4 + k];
+                acc = acc + p;
+            }
+            r[x * 4 + y] = acc;
+        }
+    memcpy(M_rgb, r, sizeof(r));
+    return GPS_OK;
+}
+
+int gps_tsdf_integrate_rgb(const gps_tsdf_state* sp, const float* M, const gps_colour_camera* cam, gps_stream stream) {
+    GPS_ENTER();
+    GPS_REQUIRE(sp != nullptr && M != nullptr && cam != nullptr);
+    GPS_REQUIRE(state_valid(*sp));
+    GPS_REQUIRE(colour_camera_valid(*cam));
+    TsdfState s = *sp;
+    ColourCam c;
+    gps_rgbd_m_rgb(cam->depth_to_rgb, M, c.M.m);
+    c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy;
+    c.W = cam->width; c.H = cam->height;
+    c.rgb = reinterpret_cast<const uchar4*>(cam->rgb);
+    // the grid of gps_tsdf_integrate; phase 1 is the same code, so the same choice between the two division sequences
+    if (div_known_safe(s.mu)) gps::launch_kernel(gps::TK_INTEGRATE, 0, integrate_kernel<true, ColourCam>, dim3(GPS_INTEGRATE_WGS), dim3(256), 0, (hipStream_t)stream, s, load_mat(M), c);
+    else gps::launch_kernel(gps::TK_INTEGRATE, 0, integrate_kernel<false, ColourCam>, dim3(GPS_INTEGRATE_WGS), dim3(256), 0, (hipStream_t)stream, s, load_mat(M), c);
     GPS_LAUNCH_CHECK();
     return GPS_OK;
 }

@@ -19,6 +19,11 @@
 // How it runs is new: one launch per pass, a 256-thread workgroup per 32x8 tile of outputs that stages the 36x12 inputs in LDS
 // with row-contiguous loads; pass 1 reads the int16 millimetre image and converts on the way in (convert_depth_kernel's
 // arithmetic), pass 5 writes s->depth, every pass writes its own ring of zeros: five launches, no conversion, memset or copy.
+// With a depth calibration (gps_tsdf_convert_filter_depth_calib) the calibrated conversion is a launch of its own into s->depth
+// and the five passes all read float images: six launches, the five above untouched.
+//
+// Also here, as the other half of view building with a full ITMRGBDCalib: the colour image registered to the depth camera
+// (register_colour_kernel, gps_tsdf_register_colour) -- ours, not the reference's.
 #include "launch_timing.hpp"
 #include "tsdf_common.hpp"
 
@@ -73,6 +78,57 @@ __global__ __launch_bounds__(256) void filter_depth_kernel(int W, int H, const i
     *o = final_depth / w_sum;
 }
 
+// Colour registered to the depth camera (gps_tsdf_register_colour) -- ours, not the reference's: per depth pixel, unproject with
+// the depth intrinsics, transform with calib_inv, project with the colour intrinsics, sample as interpolateBilinear does
+// (ITMPixelUtils.h:13-29: taps b, c, d count only where their weight is non-zero) and round to nearest.  No occlusion test.
+struct RegisterArgs {
+    int W, H;                       // depth image
+    float fx, fy, cx, cy;           // depth intrinsics
+    gpst::Mat4 T;                   // calib_inv: depth camera -> colour camera
+    int Wc, Hc;                     // colour image
+    float fxc, fyc, cxc, cyc;
+};
+
+__global__ __launch_bounds__(256) void register_colour_kernel(RegisterArgs a, const float* __restrict__ depth, const uchar4* __restrict__ rgb,
+                                                              uchar4* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.W * a.H) return;
+    const int y = i / a.W, x = i - y * a.W;
+    uchar4 o = make_uchar4(0, 0, 0, 0);
+    const float z = depth[i];
+    if (z > 0.0f) {
+        const float X = z * (((float)x - a.cx) / a.fx);
+        const float Y = z * (((float)y - a.cy) / a.fy);
+        float px, py, pz;
+        gpst::mul_point(a.T, X, Y, z, 1.0f, px, py, pz);
+        if (pz > 0.0f) {
+            const float u = a.fxc * px / pz + a.cxc;
+            const float v = a.fyc * py / pz + a.cyc;
+            // (written so that a NaN coordinate is outside)
+            if (u >= 1 && u <= a.Wc - 2 && v >= 1 && v <= a.Hc - 2) {
+                const int qx = (int)floorf(u), qy = (int)floorf(v);
+                const float dx = u - (float)qx, dy = v - (float)qy;
+                const uchar4 ta = rgb[qx + qy * a.Wc];
+                uchar4 tb = rgb[(qx + 1) + qy * a.Wc], tc = rgb[qx + (qy + 1) * a.Wc], td = rgb[(qx + 1) + (qy + 1) * a.Wc];
+                const uchar4 zero4 = make_uchar4(0, 0, 0, 0);
+                if (!(dx != 0)) tb = zero4;
+                if (!(dy != 0)) tc = zero4;
+                if (!(dx != 0 && dy != 0)) td = zero4;
+                int c[3];
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const float fa = k == 0 ? ta.x : k == 1 ? ta.y : ta.z, fb = k == 0 ? tb.x : k == 1 ? tb.y : tb.z;
+                    const float fc = k == 0 ? tc.x : k == 1 ? tc.y : tc.z, fd = k == 0 ? td.x : k == 1 ? td.y : td.z;
+                    const float m = ((fa * (1.0f - dx) * (1.0f - dy) + fb * dx * (1.0f - dy)) + fc * (1.0f - dx) * dy) + fd * dx * dy;
+                    c[k] = max(0, min(255, (int)(m + 0.5f)));
+                }
+                o = make_uchar4((unsigned char)c[0], (unsigned char)c[1], (unsigned char)c[2], 255);
+            }
+        }
+    }
+    out[i] = o;
+}
+
 }  // namespace
 
 extern "C" {
@@ -100,6 +156,45 @@ int gps_tsdf_convert_filter_depth(const gps_tsdf_state* s, const int16_t* depth_
     gps::launch_kernel(gps::TK_FILTER_DEPTH, 0, filter_depth_kernel<false>, grid, dim3(256), 0, st, W, H, (const int16_t*)nullptr, (const float*)b, a);
     gps::launch_kernel(gps::TK_FILTER_DEPTH, 0, filter_depth_kernel<false>, grid, dim3(256), 0, st, W, H, (const int16_t*)nullptr, (const float*)a, b);
     gps::launch_kernel(gps::TK_FILTER_DEPTH, 0, filter_depth_kernel<false>, grid, dim3(256), 0, st, W, H, (const int16_t*)nullptr, (const float*)b, s->depth);
+    GPS_LAUNCH_CHECK();
+    return GPS_OK;
+}
+
+int gps_tsdf_convert_filter_depth_calib(const gps_tsdf_state* s, const int16_t* raw, const gps_depth_calib* calib, void* scratch,
+                                        gps_stream stream) {
+    GPS_ENTER();
+    GPS_REQUIRE(scratch != nullptr && (reinterpret_cast<uintptr_t>(scratch) & 3) == 0);
+    // (the state, the raw image and the calibration are checked by the conversion, before its launch)
+    const int r = gps_tsdf_convert_depth_calib(s, raw, calib, stream);
+    if (r != GPS_OK) return r;
+    const int W = s->width, H = s->height;
+    hipStream_t st = (hipStream_t)stream;
+    float* a = static_cast<float*>(scratch);
+    float* b = a + (int64_t)W * H;
+    const dim3 grid(gps_div_up(W, TW), gps_div_up(H, TH));
+    // the reference's own sequence (ITMViewBuilder_CPU.cpp:56-61): depth -> a -> b -> a -> b -> depth
+    const float* src[5] = {s->depth, a, b, a, b};
+    float* dst[5] = {a, b, a, b, s->depth};
+    for (int p = 0; p < 5; p++)
+        gps::launch_kernel(gps::TK_FILTER_DEPTH, 0, filter_depth_kernel<false>, grid, dim3(256), 0, st, W, H, (const int16_t*)nullptr, src[p], dst[p]);
+    GPS_LAUNCH_CHECK();
+    return GPS_OK;
+}
+
+int gps_tsdf_register_colour(const gps_tsdf_state* s, const gps_colour_camera* cam, uint8_t* out_rgba8, gps_stream stream) {
+    GPS_ENTER();
+    GPS_REQUIRE(s != nullptr && cam != nullptr && out_rgba8 != nullptr);
+    GPS_REQUIRE(s->width > 0 && s->height > 0 && s->depth != nullptr);
+    GPS_REQUIRE(gpst::colour_camera_valid(*cam) && (reinterpret_cast<uintptr_t>(out_rgba8) & 3) == 0);
+    RegisterArgs a;
+    a.W = s->width; a.H = s->height;
+    a.fx = s->fx; a.fy = s->fy; a.cx = s->cx; a.cy = s->cy;
+    a.T = gpst::load_mat(cam->depth_to_rgb);
+    a.Wc = cam->width; a.Hc = cam->height;
+    a.fxc = cam->fx; a.fyc = cam->fy; a.cxc = cam->cx; a.cyc = cam->cy;
+    const int P = a.W * a.H;
+    register_colour_kernel<<<gps_div_up(P, 256), 256, 0, (hipStream_t)stream>>>(a, s->depth, reinterpret_cast<const uchar4*>(cam->rgb),
+                                                                                 reinterpret_cast<uchar4*>(out_rgba8));
     GPS_LAUNCH_CHECK();
     return GPS_OK;
 }

@@ -493,8 +493,76 @@ PYBIND11_MODULE(_host, m) {
         return t.use_bilateral_filter;
     });
 
+    // ---- ITMRGBDCalib and the calib.txt of ITMCalibIO.cpp
+    py::class_<ITMLib::ITMRGBDCalib>(m, "ITMRGBDCalib")
+        .def(py::init<>())
+        .def("setIntrinsicsRgb", [](ITMLib::ITMRGBDCalib& c, int w, int h, float fx, float fy, float cx, float cy) { c.intrinsics_rgb.SetFrom(w, h, fx, fy, cx, cy); })
+        .def("setIntrinsicsD", [](ITMLib::ITMRGBDCalib& c, int w, int h, float fx, float fy, float cx, float cy) { c.intrinsics_d.SetFrom(w, h, fx, fy, cx, cy); })
+        .def("setExtrinsics", [](ITMLib::ITMRGBDCalib& c, const std::vector<float>& calib16) {   // ORUtils layout
+            TORCH_CHECK(calib16.size() == 16, "setExtrinsics: 16 values in ORUtils layout");
+            ITMLib::Matrix4f m;
+            for (int i = 0; i < 16; i++) m.m[i] = calib16[i];
+            c.trafo_rgb_to_depth.SetFrom(m);
+        })
+        .def("setDisparityCalib", [](ITMLib::ITMRGBDCalib& c, float a, float b, int type) {
+            TORCH_CHECK(type == 0 || type == 1, "setDisparityCalib: type is 0 (Kinect) or 1 (affine)");
+            c.disparityCalib.SetFrom(a, b, (ITMLib::ITMDisparityCalib::TrafoType)type);
+        })
+        .def("intrinsicsRgb", [](const ITMLib::ITMRGBDCalib& c) {
+            const auto& k = c.intrinsics_rgb;
+            return py::make_tuple(k.imgSize.x, k.imgSize.y, k.projectionParamsSimple.fx, k.projectionParamsSimple.fy, k.projectionParamsSimple.px, k.projectionParamsSimple.py);
+        })
+        .def("intrinsicsD", [](const ITMLib::ITMRGBDCalib& c) {
+            const auto& k = c.intrinsics_d;
+            return py::make_tuple(k.imgSize.x, k.imgSize.y, k.projectionParamsSimple.fx, k.projectionParamsSimple.fy, k.projectionParamsSimple.px, k.projectionParamsSimple.py);
+        })
+        .def("calib", [](const ITMLib::ITMRGBDCalib& c) { return std::vector<float>(c.trafo_rgb_to_depth.calib.m, c.trafo_rgb_to_depth.calib.m + 16); })
+        .def("calibInv", [](const ITMLib::ITMRGBDCalib& c) { return std::vector<float>(c.trafo_rgb_to_depth.calib_inv.m, c.trafo_rgb_to_depth.calib_inv.m + 16); })
+        .def("disparityCalib", [](const ITMLib::ITMRGBDCalib& c) {
+            return py::make_tuple((int)c.disparityCalib.GetType(), c.disparityCalib.GetParams().x, c.disparityCalib.GetParams().y);
+        })
+        // M_rgb = calib_inv * M_d as the integration entry forms it (gps_rgbd_m_rgb)
+        .def("mRgb", [](const ITMLib::ITMRGBDCalib& c, const std::vector<float>& M_d) {
+            TORCH_CHECK(M_d.size() == 16, "mRgb: 16 values in ORUtils layout");
+            std::vector<float> out(16);
+            gpsh::check(gps_rgbd_m_rgb(c.trafo_rgb_to_depth.calib_inv.m, M_d.data(), out.data()), "gps_rgbd_m_rgb");
+            return out;
+        });
+    m.def("readRGBDCalib", [](const std::string& path) {
+        ITMLib::ITMRGBDCalib c;
+        TORCH_CHECK(ITMLib::readRGBDCalib(path.c_str(), c), "readRGBDCalib: cannot read ", path);
+        return c;
+    });
+    m.def("parseRGBDCalib", [](const std::string& text) {
+        ITMLib::ITMRGBDCalib c;
+        std::stringstream src(text);
+        TORCH_CHECK(ITMLib::readRGBDCalib(src, c), "readRGBDCalib: cannot read the text");
+        return c;
+    });
+    m.def("writeRGBDCalib", [](const std::string& path, const ITMLib::ITMRGBDCalib& c) { ITMLib::writeRGBDCalib(path.c_str(), c); });
+    m.def("formatRGBDCalib", [](const ITMLib::ITMRGBDCalib& c) {
+        std::stringstream dest;
+        ITMLib::writeRGBDCalib(dest, c);
+        return dest.str();
+    });
+    // colour registered to the depth camera (gps_tsdf_register_colour; ours): depth float [Hd, Wd] metres, the depth intrinsics
+    // (fx, fy, cx, cy), the calibration's colour camera and extrinsics, rgb uint8 [Hc, Wc, 4] -> uint8 [Hd, Wd, 4]
+    m.def("registerColour", &registerColour);
+
     // ---- TSDF engine
     py::class_<TsdfEngine>(m, "ITMBasicEngine")
+        // ITMBasicEngine(settings, calib, imgSize_rgb, imgSize_d) with the full calibration: the sizes are the calibration's
+        .def(py::init([](const ITMLib::ITMRGBDCalib& calib, float voxel_size, float mu, float vmin, float vmax) -> TsdfEngine* {
+                 ITMLib::ITMLibSettings settings;
+                 settings.sceneParams.voxelSize = voxel_size; settings.sceneParams.mu = mu;
+                 settings.sceneParams.viewFrustum_min = vmin; settings.sceneParams.viewFrustum_max = vmax;
+                 return new ITMLib::ITMBasicEngine<ITMVoxel, ITMVoxelIndex>(&settings, calib, calib.intrinsics_rgb.imgSize, calib.intrinsics_d.imgSize);
+             }),
+             py::arg("calib"), py::arg("voxel_size") = 0.005f, py::arg("mu") = 0.02f, py::arg("view_frustum_min") = 0.2f,
+             py::arg("view_frustum_max") = 10.0f)
+        .def("hasCalibration", &TsdfEngine::hasCalibration)
+        .def("registeredColour", &TsdfEngine::registeredColour)
+        .def("rgbImageSize", [](TsdfEngine& e) { const Vector2i s = e.GetRGBImageSize(); return py::make_tuple(s.x, s.y); })
         .def(py::init([](int w, int h, float fx, float fy, float cx, float cy, float voxel_size, float mu, float vmin,
                          float vmax) { return new TsdfEngine(w, h, fx, fy, cx, cy, voxel_size, mu, vmin, vmax); }),
              py::arg("width"), py::arg("height"), py::arg("fx"), py::arg("fy"), py::arg("cx"), py::arg("cy"),
@@ -641,10 +709,12 @@ PYBIND11_MODULE(_host, m) {
                 in.SetFrom(e.state().width, e.state().height, (*intrinsics)[0], (*intrinsics)[1], (*intrinsics)[2], (*intrinsics)[3]);
             }
             if (to_host) {   // the reference's signature: into a caller's host image (synchronous)
-                ITMUChar4Image img(Vector2i(e.state().width, e.state().height), true, false);
+                // (the original colour image has the colour camera's size)
+                const Vector2i dims = t == T::InfiniTAM_IMAGE_ORIGINAL_RGB ? e.GetRGBImageSize() : Vector2i(e.state().width, e.state().height);
+                ITMUChar4Image img(dims, true, false);
                 std::memset(img.GetData(MEMORYDEVICE_CPU), 0xAB, img.dataSize() * 4);   // (shows an image left untouched)
                 e.GetImage(&img, t, c2w ? &pose : nullptr, intrinsics ? &in : nullptr);
-                return py::cast(img.host_tensor().clone().view({e.state().height, e.state().width, 4}));
+                return py::cast(img.host_tensor().clone().view({dims.y, dims.x, 4}));
             }
             torch::Tensor r = e.getImageTensor(t, c2w ? &pose : nullptr, intrinsics ? &in : nullptr);
             return r.defined() ? py::cast(r) : py::none();

@@ -55,9 +55,19 @@ public:
                      settings->sceneParams.voxelSize, settings->sceneParams.mu, settings->sceneParams.viewFrustum_min,
                      settings->sceneParams.viewFrustum_max, settings->noTotalEntries_blocks, settings->noBuckets,
                      settings->excessListSize) {
-        TORCH_CHECK(imgSize_d.x == -1 || (imgSize_d.x == imgSize_rgb.x && imgSize_d.y == imgSize_rgb.y),
-                    "rgb and depth images of one size (as createTsdfEngine passes them)");
         intrinsics_d = calib.intrinsics_d;
+        // one camera with the standard calibration (what createTsdfEngine passes): the engine as it always ran.  Anything else --
+        // another colour size, colour intrinsics or pose, a disparity calibration -- is the full ITMRGBDCalib (setCalibration)
+        const bool sameSize = imgSize_d.x == -1 || (imgSize_d.x == imgSize_rgb.x && imgSize_d.y == imgSize_rgb.y);
+        const ITMExtrinsics identity;
+        const bool oneCamera = sameSize && std::memcmp(calib.trafo_rgb_to_depth.calib.m, identity.calib.m, 64) == 0 &&
+                               std::memcmp(&calib.intrinsics_rgb.projectionParamsSimple.all, &calib.intrinsics_d.projectionParamsSimple.all, 16) == 0;
+        if (!oneCamera || !calib.disparityCalib.isStandard()) {
+            ITMRGBDCalib c = calib;
+            c.intrinsics_rgb.imgSize = imgSize_rgb;
+            c.intrinsics_d.imgSize = GetImageSize();
+            setCalibration(c);
+        }
     }
 
     ITMTrackingState* GetTrackingState(void) override { return TsdfEngine::GetTrackingState(); }

@@ -109,7 +109,14 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
                     rgb_u8.size(-1) == 4, "rgb must be a contiguous uint8 [H,W,4] device tensor (uchar4)");
     TORCH_CHECK(depth_mm_i16.is_cuda() && depth_mm_i16.scalar_type() == torch::kInt16 && depth_mm_i16.is_contiguous(),
                 "depth must be a contiguous int16 [H,W] device tensor (millimetres)");
-    {
+    if (has_cam_) {   // the colour camera's image, kept in a buffer of the engine's own; state_.rgb is not read by the integration
+        TORCH_CHECK(rgb_u8.dim() == 3 && rgb_u8.size(0) == cam_.height && rgb_u8.size(1) == cam_.width,
+                    "ProcessFrame: the colour image is not of the colour camera's size");
+        TORCH_CHECK(depth_mm_i16.numel() == (int64_t)state_.width * state_.height, "ProcessFrame: the depth image is not of the depth camera's size");
+        rgb_c_.copy_(rgb_u8);
+        std::lock_guard<std::mutex> lk(state_mu_);
+        frame_inputs_ = {rgb_c_, depth_mm_i16};
+    } else {
         std::lock_guard<std::mutex> lk(state_mu_);
         frame_inputs_ = {rgb_u8, depth_mm_i16};  // keep alive while kernels may read them
         state_.rgb = ptr<uint8_t>(rgb_u8);
@@ -120,12 +127,12 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         if (!track_scratch_.defined()) turnOnTracking();  // ITMLibSettings defaults
         std::function<void()> gate;
         gate.swap(beforeNextFusion);
-        if (useBilateralFilter) filterDepth(depth_mm_i16);   // (the halves below then read state_.depth: depth_mm NULL)
-        if (useApproximateRaycast || useBilateralFilter) {   // the same two halves, Prepare with the forward render if asked to
-            check(gps_tsdf_frame_track(&state_, useBilateralFilter ? nullptr : ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_, track_scratch_.data_ptr(),
+        if (convertsAhead()) convertAhead(depth_mm_i16);   // (the halves below then read state_.depth: depth_mm NULL)
+        if (useApproximateRaycast || convertsAhead()) {   // the same two halves, Prepare with the forward render if asked to
+            check(gps_tsdf_frame_track(&state_, convertsAhead() ? nullptr : ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_, track_scratch_.data_ptr(),
                                        track_scratch_.numel(), current_stream()), "gps_tsdf_frame_track");
             if (gate) gate();
-            check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 1, 0, forwardBlock(), useApproximateRaycast ? 1 : 0, current_stream()),
+            check(mapHalf(&track_state_, 1, 0, current_stream()),
                   "gps_tsdf_frame_map_fwd");
         } else {
             check(gps_tsdf_process_frame_tracked_gated(&state_, ptr<int16_t>(depth_mm_i16), &track_cfg_, &track_state_,
@@ -144,10 +151,10 @@ ITMTrackingState* TsdfEngine::ProcessFrame(const torch::Tensor& rgb_u8, const to
         pose_d_.SetInvM(c2w.data_ptr<float>());
         pose_d_.Coerce();
         if (beforeNextFusion) { std::function<void()> gate; gate.swap(beforeNextFusion); gate(); }
-        if (useBilateralFilter) {   // the filtered depth is in place: the rest of gps_tsdf_process_frame_fwd at the given pose
-            filterDepth(depth_mm_i16);
+        if (convertsAhead()) {   // the view's depth is in place: the rest of gps_tsdf_process_frame_fwd at the given pose
+            convertAhead(depth_mm_i16);
             memcpy(track_state_.pose_M, pose_d_.GetM(), 64); memcpy(track_state_.pose_invM, pose_d_.GetInvM(), 64);
-            check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 1, 0, forwardBlock(), useApproximateRaycast ? 1 : 0, current_stream()),
+            check(mapHalf(&track_state_, 1, 0, current_stream()),
                   "gps_tsdf_frame_map_fwd");
         } else
         // (gps_tsdf_process_frame's launches; Prepare runs with tracking off too -- ITMBasicEngine.tpp:355 -- and keeps the point
@@ -176,8 +183,77 @@ void TsdfEngine::ensureRelocaliser() {   // ITMBasicEngine.tpp:57-60
 void TsdfEngine::convertDepth(const torch::Tensor& depth_mm_i16) {
     TORCH_CHECK(depth_mm_i16.is_cuda() && depth_mm_i16.scalar_type() == torch::kInt16 && depth_mm_i16.is_contiguous() &&
                     depth_mm_i16.numel() == (int64_t)state_.width * state_.height, "depth must be a contiguous int16 [H,W] device tensor");
-    if (useBilateralFilter) return filterDepth(depth_mm_i16);
-    check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), current_stream()), "gps_tsdf_convert_depth");
+    convertAhead(depth_mm_i16);
+}
+
+// UpdateView's switch on the disparity calibration, then the filter when it is on (ITMViewBuilder_CPU.cpp:41-62)
+void TsdfEngine::convertAhead(const torch::Tensor& raw_i16) {
+    if (!has_depth_calib_) {
+        if (useBilateralFilter) return filterDepth(raw_i16);
+        check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(raw_i16), current_stream()), "gps_tsdf_convert_depth");
+        return;
+    }
+    TORCH_CHECK(raw_i16.numel() == (int64_t)state_.width * state_.height, "depth must have the engine's image size");
+    if (!useBilateralFilter) {
+        check(gps_tsdf_convert_depth_calib(&state_, ptr<int16_t>(raw_i16), &depth_calib_, current_stream()), "gps_tsdf_convert_depth_calib");
+        return;
+    }
+    if (!filter_scratch_.defined()) filter_scratch_ = zeros_bytes(gps_tsdf_filter_scratch_bytes(state_.width, state_.height), device_);
+    check(gps_tsdf_convert_filter_depth_calib(&state_, ptr<int16_t>(raw_i16), &depth_calib_, filter_scratch_.data_ptr(), current_stream()),
+          "gps_tsdf_convert_filter_depth_calib");
+}
+
+void TsdfEngine::setCalibration(const ITMLib::ITMRGBDCalib& calib) {
+    TORCH_CHECK(framesSeen == 0, "setCalibration: call it before the first frame");
+    const auto& kd = calib.intrinsics_d;
+    TORCH_CHECK(kd.imgSize.x == state_.width && kd.imgSize.y == state_.height, "setCalibration: intrinsics_d is not of the engine's depth size");
+    const auto& kc = calib.intrinsics_rgb;
+    TORCH_CHECK(kc.imgSize.x > 0 && kc.imgSize.y > 0, "setCalibration: the colour image size must be positive");
+    calib_ = calib;
+    state_.fx = kd.projectionParamsSimple.fx; state_.fy = kd.projectionParamsSimple.fy;
+    state_.cx = kd.projectionParamsSimple.px; state_.cy = kd.projectionParamsSimple.py;
+    intrinsics_d = kd;
+    cam_.width = kc.imgSize.x; cam_.height = kc.imgSize.y;
+    cam_.fx = kc.projectionParamsSimple.fx; cam_.fy = kc.projectionParamsSimple.fy;
+    cam_.cx = kc.projectionParamsSimple.px; cam_.cy = kc.projectionParamsSimple.py;
+    memcpy(cam_.depth_to_rgb, calib.trafo_rgb_to_depth.calib_inv.m, 64);
+    rgb_c_ = zeros_bytes((int64_t)cam_.width * cam_.height * 4, device_).view({cam_.height, cam_.width, 4});
+    cam_.rgb = ptr<uint8_t>(rgb_c_);
+    has_cam_ = true;
+    has_depth_calib_ = !calib.disparityCalib.isStandard();
+    depth_calib_.type = calib.disparityCalib.GetType() == ITMLib::ITMDisparityCalib::TRAFO_KINECT ? GPS_DEPTH_CALIB_KINECT : GPS_DEPTH_CALIB_AFFINE;
+    depth_calib_.a = calib.disparityCalib.GetParams().x; depth_calib_.b = calib.disparityCalib.GetParams().y;
+}
+
+torch::Tensor registerColour(const torch::Tensor& depth_f, const std::vector<float>& intrinsics_d, const ITMLib::ITMRGBDCalib& calib,
+                             const torch::Tensor& rgb_u8) {
+    const auto& kc = calib.intrinsics_rgb;
+    TORCH_CHECK(depth_f.is_cuda() && depth_f.scalar_type() == torch::kFloat32 && depth_f.is_contiguous() && depth_f.dim() == 2,
+                "registerColour: depth must be a contiguous float [H,W] device tensor");
+    TORCH_CHECK(rgb_u8.is_cuda() && rgb_u8.scalar_type() == torch::kUInt8 && rgb_u8.is_contiguous() && rgb_u8.dim() == 3 &&
+                    rgb_u8.size(0) == kc.imgSize.y && rgb_u8.size(1) == kc.imgSize.x && rgb_u8.size(2) == 4,
+                "registerColour: rgb must be a contiguous uint8 [H,W,4] device tensor of the calibration's colour size");
+    TORCH_CHECK(intrinsics_d.size() == 4, "registerColour: intrinsics_d are (fx, fy, cx, cy)");
+    gps_tsdf_state s{};
+    s.width = (int)depth_f.size(1); s.height = (int)depth_f.size(0);
+    s.fx = intrinsics_d[0]; s.fy = intrinsics_d[1]; s.cx = intrinsics_d[2]; s.cy = intrinsics_d[3];
+    s.depth = depth_f.data_ptr<float>();
+    gps_colour_camera cam{};
+    cam.width = kc.imgSize.x; cam.height = kc.imgSize.y;
+    cam.fx = kc.projectionParamsSimple.fx; cam.fy = kc.projectionParamsSimple.fy;
+    cam.cx = kc.projectionParamsSimple.px; cam.cy = kc.projectionParamsSimple.py;
+    memcpy(cam.depth_to_rgb, calib.trafo_rgb_to_depth.calib_inv.m, 64);
+    cam.rgb = rgb_u8.data_ptr<uint8_t>();
+    torch::Tensor out = torch::empty({s.height, s.width, 4}, rgb_u8.options());
+    check(gps_tsdf_register_colour(&s, &cam, out.data_ptr<uint8_t>(), current_stream()), "gps_tsdf_register_colour");
+    return out;
+}
+
+torch::Tensor TsdfEngine::registeredColour() {
+    TORCH_CHECK(has_cam_ && framesSeen > 0, "registeredColour: needs setCalibration and a processed frame");
+    torch::Tensor out = zeros_bytes((int64_t)state_.width * state_.height * 4, device_).view({state_.height, state_.width, 4});
+    check(gps_tsdf_register_colour(&state_, &cam_, ptr<uint8_t>(out), current_stream()), "gps_tsdf_register_colour");
+    return out;
 }
 
 void TsdfEngine::filterDepth(const torch::Tensor& depth_mm_i16) {
@@ -194,7 +270,7 @@ void TsdfEngine::relocaliseFromPose(const float* M, const float* invM) {
     float m[16], im[16];   // (M / invM may point into the tracking state)
     memcpy(m, M, 64); memcpy(im, invM, 64);
     memcpy(track_state_.pose_M, m, 64); memcpy(track_state_.pose_invM, im, 64);
-    check(gps_tsdf_frame_map_fwd(&state_, &track_state_, 0, 1, forwardBlock(), useApproximateRaycast ? 1 : 0, st), "gps_tsdf_frame_map_fwd");
+    check(mapHalf(&track_state_, 0, 1, st), "gps_tsdf_frame_map_fwd");
     check(gps_tsdf_track_camera(&state_, &track_cfg_, &track_state_, track_scratch_.data_ptr(), track_scratch_.numel(), st),
           "gps_tsdf_track_camera");
     pose_d_.SetBoth(track_state_.pose_M, track_state_.pose_invM);
@@ -212,8 +288,8 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
     if (trackingActive) {
         if (!track_scratch_.defined()) turnOnTracking();
         const bool tracks = ts.age_point_cloud != -1;
-        if (useBilateralFilter) filterDepth(depth_mm_i16);   // (frame_track then reads state_.depth: depth_mm NULL)
-        check(gps_tsdf_frame_track(&state_, useBilateralFilter ? nullptr : ptr<int16_t>(depth_mm_i16), &track_cfg_, &ts,
+        if (convertsAhead()) convertAhead(depth_mm_i16);   // (frame_track then reads state_.depth: depth_mm NULL)
+        check(gps_tsdf_frame_track(&state_, convertsAhead() ? nullptr : ptr<int16_t>(depth_mm_i16), &track_cfg_, &ts,
                                    track_scratch_.data_ptr(), track_scratch_.numel(), st), "gps_tsdf_frame_track");
         if (tracks) {
             verdict = verdictOfLastTrack();
@@ -226,8 +302,7 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
         auto c2w = gtC2wPoses[framesSeen].to(torch::kCPU, torch::kFloat32).contiguous();
         pose_d_.SetInvM(c2w.data_ptr<float>());
         memcpy(ts.pose_M, pose_d_.GetM(), 64); memcpy(ts.pose_invM, pose_d_.GetInvM(), 64);
-        if (useBilateralFilter) filterDepth(depth_mm_i16);
-        else check(gps_tsdf_convert_depth(&state_, ptr<int16_t>(depth_mm_i16), st), "gps_tsdf_convert_depth");
+        convertAhead(depth_mm_i16);
     }
     const auto forced = forced_results_.find(framesSeen);
     if (forced != forced_results_.end()) verdict = forced->second;
@@ -263,7 +338,7 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
         // write the live render state only -- visible_type / visible_ids, the live min/max and raycast images -- and the free-view
         // raycasts of a map update have scratch, lists and counters of their own.  That holds as long as nothing on the map
         // stream reads the live render state.)
-        check(gps_tsdf_frame_map_fwd(&state_, &ts, d.fuse ? 1 : 0, 0, forwardBlock(), useApproximateRaycast ? 1 : 0, st),
+        check(mapHalf(&ts, d.fuse ? 1 : 0, 0, st),
               "gps_tsdf_frame_map_fwd");
     } else {
         // (the table has one more row, fusion WITHOUT a raycast for a FAILED result before tracking is initialised; this engine
@@ -280,10 +355,11 @@ ITMTrackingState* TsdfEngine::processFrameWithFailureModes(const torch::Tensor& 
 
 ITMTrackingState* TsdfEngine::ProcessFrame(ITMUChar4Image* rgbImage, ITMShortImage* rawDepthImage) {
     TORCH_CHECK(rgbImage && rawDepthImage, "ProcessFrame: null image");
-    TORCH_CHECK(rgbImage->noDims.x == state_.width && rgbImage->noDims.y == state_.height &&
+    const Vector2i rgbSize = GetRGBImageSize();
+    TORCH_CHECK(rgbImage->noDims.x == rgbSize.x && rgbImage->noDims.y == rgbSize.y &&
                     rawDepthImage->noDims.x == state_.width && rawDepthImage->noDims.y == state_.height,
                 "ProcessFrame: image size differs from the engine's");
-    const int64_t P = (int64_t)state_.width * state_.height;
+    const int64_t P = (int64_t)state_.width * state_.height, Pc = (int64_t)rgbSize.x * rgbSize.y;
     const int slot = framesSeen & 1;
     auto on_device = [&](const torch::Tensor& dev, const torch::Tensor& host, torch::Tensor& stage, int64_t bytes) {
         if (dev.defined()) return dev;
@@ -294,9 +370,9 @@ ITMTrackingState* TsdfEngine::ProcessFrame(ITMUChar4Image* rgbImage, ITMShortIma
                                    (hipStream_t)current_stream()) == hipSuccess, "UpdateView: upload failed");
         return stage;
     };
-    auto rgb = on_device(rgbImage->tensor(), rgbImage->host_tensor(), stage_rgb_[slot], P * 4);
+    auto rgb = on_device(rgbImage->tensor(), rgbImage->host_tensor(), stage_rgb_[slot], Pc * 4);
     auto dep = on_device(rawDepthImage->tensor(), rawDepthImage->host_tensor(), stage_depth_[slot], P * 2);
-    return ProcessFrame(rgb.view({state_.height, state_.width, 4}), dep.view(torch::kInt16).view({state_.height, state_.width}));
+    return ProcessFrame(rgb.view({rgbSize.y, rgbSize.x, 4}), dep.view(torch::kInt16).view({state_.height, state_.width}));
 }
 
 void TsdfEngine::runRaycast(ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics) {
@@ -373,15 +449,21 @@ torch::Tensor TsdfEngine::getImageTensor(GetImageType type, ORUtils::SE3Pose* po
     if (framesSeen == 0) return torch::Tensor();   // (view == NULL)
     const torch::Tensor src = getImageSource(type, pose, intrinsics);
     if (!src.defined()) return zeros_bytes((int64_t)state_.width * state_.height * 4, device_).view({state_.height, state_.width, 4});
+    if (type == GetImageType::InfiniTAM_IMAGE_ORIGINAL_RGB) {   // at the colour camera's size (ITMBasicEngine.tpp:403)
+        const Vector2i c = GetRGBImageSize();
+        return src.view({c.y, c.x, 4}).clone();
+    }
     return src.view({state_.height, state_.width, 4}).clone();
 }
 
 void TsdfEngine::GetImage(ITMUChar4Image* out, GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics) {
     if (framesSeen == 0) return;   // (view == NULL)
     TORCH_CHECK(out != nullptr, "GetImage: null image");
-    TORCH_CHECK(out->noDims.x == state_.width && out->noDims.y == state_.height, "GetImage: the image must have the engine's size");
+    // (ORIGINAL_RGB answers at the colour camera's size: out->ChangeDims(view->rgb->noDims), ITMBasicEngine.tpp:403)
+    const Vector2i want = type == GetImageType::InfiniTAM_IMAGE_ORIGINAL_RGB ? GetRGBImageSize() : Vector2i(state_.width, state_.height);
+    TORCH_CHECK(out->noDims.x == want.x && out->noDims.y == want.y, "GetImage: the image must have the engine's size (the colour camera's for ORIGINAL_RGB)");
     const torch::Tensor src = getImageSource(type, pose, intrinsics);
-    const size_t bytes = (size_t)state_.width * state_.height * 4;
+    const size_t bytes = (size_t)want.x * want.y * 4;
     hipStream_t st = (hipStream_t)current_stream();
     if (out->isAllocated_CUDA()) {
         TORCH_CHECK((src.defined() ? hipMemcpyAsync(out->GetData(MEMORYDEVICE_CUDA), src.data_ptr(), bytes, hipMemcpyDeviceToDevice, st)

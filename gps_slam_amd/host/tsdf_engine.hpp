@@ -15,6 +15,9 @@
 // SaveSceneToMesh.
 #pragma once
 #include <cstring>
+#include <fstream>
+#include <sstream>
+#include <string>
 #include <memory>
 #include <functional>
 #include <mutex>
@@ -118,14 +121,128 @@ public:
     ITMIntrinsics() { SetFrom(640, 480, 580.f, 580.f, 320.f, 240.f); }  // ITMIntrinsics.cpp:11-15
 };
 
-struct ITMDisparityCalib { void SetStandard() {} };  // depth = mm * 0.001, no affine/Kinect disparity (InfiniTAM_tools.cpp:10)
+struct Vector2f { float x, y; };
+struct Matrix4f { float m[16]; };   // ORUtils layout m[col * 4 + row]
+
+// ITMLib/Objects/Camera/ITMDisparityCalib.h: raw values -> depth, 8 b fx / (a - d) (Kinect) or a d + b (affine)
+class ITMDisparityCalib {
+public:
+    enum TrafoType { TRAFO_KINECT, TRAFO_AFFINE };   // == gps_depth_calib_type
+    ITMDisparityCalib() { SetStandard(); }
+    const Vector2f& GetParams() const { return params; }
+    TrafoType GetType() const { return type; }
+    void SetFrom(float a, float b, TrafoType _type) {   // "both zero" is the standard calibration (:55-64)
+        if (a != 0.0f || b != 0.0f) { params.x = a; params.y = b; type = _type; }
+        else SetStandard();
+    }
+    void SetStandard() { SetFrom(1.0f / 1000.0f, 0.0f, TRAFO_AFFINE); }   // millimetres
+    bool isStandard() const { return type == TRAFO_AFFINE && params.x == 1.0f / 1000.0f && params.y == 0.0f; }
+
+private:
+    TrafoType type;
+    Vector2f params;
+};
+
+// ITMLib/Objects/Camera/ITMExtrinsics.h: calib takes points of the colour camera to the depth camera; calib_inv as :28-40 build it
+// (the transpose of the rotation, and -(R^T t) as three subtractions from 0, in float)
+class ITMExtrinsics {
+public:
+    Matrix4f calib, calib_inv;
+    void SetFrom(const Matrix4f& src) {
+        calib = src;
+        for (int i = 0; i < 16; i++) calib_inv.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) calib_inv.m[r + 4 * c] = calib.m[c + 4 * r];
+        for (int r = 0; r < 3; ++r) {
+            volatile float dest = 0.0f;   // (volatile: no fused multiply-subtract, whatever the host compiler's flags)
+            for (int c = 0; c < 3; ++c) { volatile float p = calib.m[c + 4 * r] * calib.m[c + 4 * 3]; dest = dest - p; }
+            calib_inv.m[r + 4 * 3] = dest;
+        }
+    }
+    ITMExtrinsics() {
+        Matrix4f m;
+        for (int i = 0; i < 16; i++) m.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        SetFrom(m);
+    }
+};
 
 // ITMLib/Objects/Camera/ITMRGBDCalib.h
 class ITMRGBDCalib {
 public:
     ITMIntrinsics intrinsics_rgb, intrinsics_d;
+    ITMExtrinsics trafo_rgb_to_depth;
     ITMDisparityCalib disparityCalib;
 };
+
+// ITMLib/Objects/Camera/ITMCalibIO.cpp: the four-part calib.txt (colour intrinsics, depth intrinsics, extrinsics, disparity
+// calibration), read and written in the reference's text format
+inline bool readIntrinsics(std::istream& src, ITMIntrinsics& dest) {
+    int width, height;
+    float f[2], c[2];
+    src >> width >> height >> f[0] >> f[1] >> c[0] >> c[1];
+    if (src.fail()) return false;
+    dest.SetFrom(width, height, f[0], f[1], c[0], c[1]);
+    return true;
+}
+inline bool readExtrinsics(std::istream& src, ITMExtrinsics& dest) {
+    Matrix4f m;
+    for (int r = 0; r < 3; r++) src >> m.m[r] >> m.m[4 + r] >> m.m[8 + r] >> m.m[12 + r];
+    m.m[3] = m.m[7] = m.m[11] = 0.0f; m.m[15] = 1.0f;
+    if (src.fail()) return false;
+    dest.SetFrom(m);
+    return true;
+}
+inline bool readDisparityCalib(std::istream& src, ITMDisparityCalib& dest) {
+    std::string word;
+    src >> word;
+    if (src.fail()) return false;
+    ITMDisparityCalib::TrafoType type = ITMDisparityCalib::TRAFO_KINECT;
+    float a, b;
+    if (word == "kinect") src >> a;
+    else if (word == "affine") { type = ITMDisparityCalib::TRAFO_AFFINE; src >> a; }
+    else {
+        std::stringstream wordstream(word);
+        wordstream >> a;
+        if (wordstream.fail()) return false;
+    }
+    src >> b;
+    if (src.fail()) return false;
+    dest.SetFrom(a, b, type);   // (both zero: the standard calibration)
+    return true;
+}
+inline bool readRGBDCalib(std::istream& src, ITMRGBDCalib& dest) {
+    return readIntrinsics(src, dest.intrinsics_rgb) && readIntrinsics(src, dest.intrinsics_d) &&
+           readExtrinsics(src, dest.trafo_rgb_to_depth) && readDisparityCalib(src, dest.disparityCalib);
+}
+inline bool readRGBDCalib(const char* fileName, ITMRGBDCalib& dest) {
+    std::ifstream f(fileName);
+    return readRGBDCalib(f, dest);
+}
+inline void writeIntrinsics(std::ostream& dest, const ITMIntrinsics& src) {
+    dest << src.imgSize.x << ' ' << src.imgSize.y << '\n';
+    dest << src.projectionParamsSimple.fx << ' ' << src.projectionParamsSimple.fy << '\n';
+    dest << src.projectionParamsSimple.px << ' ' << src.projectionParamsSimple.py << '\n';
+}
+inline void writeExtrinsics(std::ostream& dest, const ITMExtrinsics& src) {
+    const float* m = src.calib.m;
+    for (int r = 0; r < 3; r++) dest << m[r] << ' ' << m[4 + r] << ' ' << m[8 + r] << ' ' << m[12 + r] << '\n';
+}
+inline void writeDisparityCalib(std::ostream& dest, const ITMDisparityCalib& src) {
+    if (src.GetType() == ITMDisparityCalib::TRAFO_AFFINE) dest << "affine ";
+    dest << src.GetParams().x << ' ' << src.GetParams().y << '\n';
+}
+inline void writeRGBDCalib(std::ostream& dest, const ITMRGBDCalib& src) {
+    writeIntrinsics(dest, src.intrinsics_rgb);
+    dest << '\n';
+    writeIntrinsics(dest, src.intrinsics_d);
+    dest << '\n';
+    writeExtrinsics(dest, src.trafo_rgb_to_depth);
+    dest << '\n';
+    writeDisparityCalib(dest, src.disparityCalib);
+}
+inline void writeRGBDCalib(const char* fileName, const ITMRGBDCalib& src) {
+    std::ofstream f(fileName);
+    writeRGBDCalib(f, src);
+}
 
 // ITMLib/Utils/ITMSceneParams.h + ITMLibSettings.{h,cpp} (the fields createTsdfEngine sets, reference defaults :10)
 struct ITMSceneParams { float voxelSize = 0.005f, mu = 0.02f, viewFrustum_min = 0.2f, viewFrustum_max = 3.0f; int maxW = 100; };
@@ -290,6 +407,7 @@ public:
                    float mu = 0.02f, float view_frustum_min = 0.2f, float view_frustum_max = 10.0f,
                    int n_blocks = 0x40000, int n_buckets = 0x100000, int n_excess = 0x20000,
                    torch::Device device = torch::kCUDA);
+    virtual ~TsdfEngine() = default;   // (ITMBasicEngine<> is handed out and deleted through this class)
 
     void resetAll();
     // ITMBasicEngine::ProcessFrame with tracking off: pose := gtC2wPoses[framesProcessed] (ITMBasicEngine.tpp:260-385).
@@ -331,6 +449,18 @@ public:
     void setUseBilateralFilter(bool on) { useBilateralFilter = on; }
     bool usesBilateralFilter() const { return useBilateralFilter; }
     bool hasFilterScratch() const { return filter_scratch_.defined(); }   // (allocated by the option's first frame only)
+    // ---- full RGB-D calibration (ITMRGBDCalib): a colour camera of its own size, intrinsics and pose, and a disparity calibration
+    // of either type.  Call before the first frame.  Frames then carry a colour image of calib.intrinsics_rgb's size, which the
+    // engine copies into a buffer of its own; the raw image goes through the calibrated conversion; the integration projects into
+    // the colour camera (gps_tsdf_frame_map_rgb); GetImage(ORIGINAL_RGB) answers at the colour size.  Never called: one camera,
+    // millimetres, the launches this engine always issued.
+    void setCalibration(const ITMLib::ITMRGBDCalib& calib);
+    bool hasCalibration() const { return has_cam_; }
+    const ITMLib::ITMRGBDCalib& calibration() const { return calib_; }
+    Vector2i GetRGBImageSize() const { return has_cam_ ? Vector2i(cam_.width, cam_.height) : Vector2i(state_.width, state_.height); }
+    // the last frame's colour image registered to the depth camera (gps_tsdf_register_colour; OURS, not the reference's):
+    // uint8 [H, W, 4] at the depth size, alpha 255 where a colour was found, 0 0 0 0 elsewhere; no occlusion test
+    torch::Tensor registeredColour();
     int agePointCloud() const { return track_state_.age_point_cloud; }
     torch::Tensor GetForwardProjection() const;   // renderState->forwardProjection, float [H,W,4] (undefined before the first use)
     torch::Tensor GetLiveImage() const { return live_colour_; }   // uchar4 [H,W,4] of the last runRaycast(NULL, NULL)
@@ -490,6 +620,19 @@ private:
     bool useBilateralFilter = false;
     torch::Tensor filter_scratch_;
     void filterDepth(const torch::Tensor& depth_mm_i16);   // UpdateView with the filter: conversion + five passes into state_.depth
+    // the calibration: the colour camera (its image pointer names rgb_c_), the depth calibration when it is not the standard one
+    ITMLib::ITMRGBDCalib calib_;
+    bool has_cam_ = false, has_depth_calib_ = false;
+    gps_colour_camera cam_{};
+    gps_depth_calib depth_calib_{};
+    torch::Tensor rgb_c_;
+    // UpdateView's depth half ahead of the frame's entry points (the filter and / or a calibration: depth_mm NULL afterwards)
+    bool convertsAhead() const { return useBilateralFilter || has_cam_; }
+    void convertAhead(const torch::Tensor& raw_i16);
+    // gps_tsdf_frame_map_fwd, with the colour camera when there is one (NULL: exactly that call)
+    int mapHalf(gps_track_state* ts, int fuse, int reset_visible, gps_stream st) {
+        return gps_tsdf_frame_map_rgb(&state_, ts, fuse, reset_visible, forwardBlock(), useApproximateRaycast ? 1 : 0, has_cam_ ? &cam_ : nullptr, st);
+    }
     torch::Tensor fwd_block_, live_colour_;
     torch::Tensor kf_raycast_, depth_colour_, depth_colour_scratch_;   // GetImage: kfRaycast (never written), DepthToUchar4's image and limits
     torch::Tensor getImageSource(GetImageType type, ORUtils::SE3Pose* pose, ITMLib::ITMIntrinsics* intrinsics);
@@ -502,3 +645,10 @@ private:
     ITMUChar4Image free_image_;
     ITMFloat4Image free_vertex_, live_vertex_;
 };
+
+// Colour registered to the depth camera, without an engine (gps_tsdf_register_colour; OURS, not the reference's): depth_f float
+// [Hd, Wd] device tensor in metres (<= 0: invalid), intrinsics_d = (fx, fy, cx, cy) of the depth camera, the calibration's colour
+// camera and extrinsics, rgb uint8 [Hc, Wc, 4] device tensor -> uint8 [Hd, Wd, 4], alpha 255 where a colour was found, 0 0 0 0
+// elsewhere.  One launch on the current stream, no host read, no occlusion test.
+torch::Tensor registerColour(const torch::Tensor& depth_f, const std::vector<float>& intrinsics_d, const ITMLib::ITMRGBDCalib& calib,
+                             const torch::Tensor& rgb_u8);

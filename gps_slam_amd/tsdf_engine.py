@@ -14,6 +14,7 @@ import weakref
 import torch
 
 from ._lib import TrackConfig, TrackState, TsdfState, check, lib
+from .rgbd_calib import RGBDCalib, read_rgbd_calib, register_colour, write_rgbd_calib  # noqa: F401  (the calibration's surface)
 
 # reference capacities (ITMLib/Objects/Scene/ITMVoxelBlockHash.h:18-22)
 SDF_LOCAL_BLOCK_NUM = 0x40000
@@ -78,8 +79,24 @@ class TsdfEngine:
     def __init__(self, width, height, fx, fy, cx, cy, voxel_size=0.005, mu=0.02, view_frustum_min=0.2,
                  view_frustum_max=10.0, n_blocks=SDF_LOCAL_BLOCK_NUM, n_buckets=SDF_BUCKET_NUM,
                  n_excess=SDF_EXCESS_LIST_SIZE, device="cuda:0", use_approximate_raycast=False,
-                 use_bilateral_filter=False):
+                 use_bilateral_filter=False, calib=None):
         self.W, self.H = int(width), int(height)
+        # calib (an rgbd_calib.RGBDCalib): the full ITMRGBDCalib.  Its depth intrinsics replace fx, fy, cx, cy; its colour camera
+        # (any size, intrinsics and pose) is the one the integration projects into; a disparity calibration other than the
+        # standard one converts the raw image.  None: one camera, millimetres -- the launches this engine always issued.
+        self.calib = calib
+        self._cam = self._depth_calib = self._rgb_c = None
+        if calib is not None:
+            kd = calib.intrinsics_d
+            if (kd.width, kd.height) != (self.W, self.H):
+                raise ValueError("TsdfEngine: calib.intrinsics_d is %dx%d, the engine's depth image %dx%d" % (kd.width, kd.height, self.W, self.H))
+            fx, fy, cx, cy = kd.params()
+            self._cam = calib.colour_camera()
+            self.W_rgb, self.H_rgb = self._cam.width, self._cam.height
+            if not calib.disparityCalib.is_standard():
+                self._depth_calib = calib.disparityCalib.as_struct()
+        else:
+            self.W_rgb, self.H_rgb = self.W, self.H
         # ITMLibSettings::useBilateralFilter: UpdateView runs five passes of the bilateral depth filter behind the conversion
         self.use_bilateral_filter = bool(use_bilateral_filter)
         self._filter_scratch = None
@@ -154,37 +171,83 @@ class TsdfEngine:
             self._fwd_block = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
         return self._fwd_block.data_ptr()
 
-    def _filter_depth(self, depth_mm_i16):
-        """UpdateView with useBilateralFilter: conversion + five filter passes into the state's depth (gps_tsdf_convert_filter_depth)"""
+    def _filter_scratch_ptr(self):
         if self._filter_scratch is None:
             nbytes = int(lib.gps_tsdf_filter_scratch_bytes(self.W, self.H))
             self._filter_scratch = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
-        check(lib.gps_tsdf_convert_filter_depth(C.byref(self.state), depth_mm_i16.data_ptr(), self._filter_scratch.data_ptr(),
-                                                self._stream()), "gps_tsdf_convert_filter_depth")
+        return self._filter_scratch.data_ptr()
+
+    def _converts_ahead(self):
+        """the view's depth is written before the frame's entry points run (they then take depth_mm NULL): the filter, a calibration"""
+        return self.use_bilateral_filter or self._cam is not None
+
+    def _convert_ahead(self, raw_i16):
+        """UpdateView's depth half: the conversion the calibration asks for (standard when there is none), then the five filter
+        passes when the filter is on, into the state's depth"""
+        s, raw, st = C.byref(self.state), raw_i16.data_ptr(), self._stream()
+        if self._depth_calib is None:
+            if self.use_bilateral_filter:
+                check(lib.gps_tsdf_convert_filter_depth(s, raw, self._filter_scratch_ptr(), st), "gps_tsdf_convert_filter_depth")
+            else:
+                check(lib.gps_tsdf_convert_depth(s, raw, st), "gps_tsdf_convert_depth")
+        elif self.use_bilateral_filter:
+            check(lib.gps_tsdf_convert_filter_depth_calib(s, raw, C.byref(self._depth_calib), self._filter_scratch_ptr(), st),
+                  "gps_tsdf_convert_filter_depth_calib")
+        else:
+            check(lib.gps_tsdf_convert_depth_calib(s, raw, C.byref(self._depth_calib), st), "gps_tsdf_convert_depth_calib")
+
+    def _map_half(self):
+        """gps_tsdf_frame_map_fwd, with the colour camera when there is one (a NULL camera is exactly that call)"""
+        check(lib.gps_tsdf_frame_map_rgb(C.byref(self.state), C.byref(self.track_state), 1, 0, self._forward_block(),
+                                         1 if self.use_approximate_raycast else 0, C.byref(self._cam) if self._cam is not None else None,
+                                         self._stream()), "gps_tsdf_frame_map_rgb")
+
+    def _take_inputs(self, rgb_u8, raw_i16):
+        """the frame's images: read in place with one camera; with calib= the colour image, of the COLOUR camera's size, is copied
+        into a buffer of the engine's own"""
+        if rgb_u8.shape[-1] == 3:
+            rgb_u8 = torch.cat([rgb_u8, torch.full_like(rgb_u8[..., :1], 255)], -1)
+        assert rgb_u8.is_contiguous() and raw_i16.is_contiguous()
+        if self._cam is None:
+            self._frame_inputs = (rgb_u8, raw_i16)  # keep alive while kernels may read them
+            self.state.rgb = rgb_u8.data_ptr()
+            return
+        if tuple(rgb_u8.shape) != (self.H_rgb, self.W_rgb, 4):
+            raise ValueError("ProcessFrame: the colour image is %s, the colour camera %dx%d" % (tuple(rgb_u8.shape), self.W_rgb, self.H_rgb))
+        assert tuple(raw_i16.shape) == (self.H, self.W)
+        if self._rgb_c is None:
+            self._rgb_c = torch.zeros((self.H_rgb, self.W_rgb, 4), dtype=torch.uint8, device=self.device)
+        self._rgb_c.copy_(rgb_u8)
+        self._cam.rgb = self._rgb_c.data_ptr()
+        self._frame_inputs = (self._rgb_c, raw_i16)
+
+    def registeredColour(self):
+        """the last frame's colour image registered to the depth camera (gps_tsdf_register_colour; ours, not the reference's):
+        uint8 [H, W, 4] at the DEPTH size, alpha 255 where a colour was found, 0 0 0 0 elsewhere.  No occlusion test."""
+        if self._cam is None or self._rgb_c is None:
+            raise RuntimeError("registeredColour: needs calib= and a processed frame")
+        out = torch.empty((self.H, self.W, 4), dtype=torch.uint8, device=self.device)
+        check(lib.gps_tsdf_register_colour(C.byref(self.state), C.byref(self._cam), out.data_ptr(), self._stream()), "gps_tsdf_register_colour")
+        return out
 
     # ---- ITMBasicEngine::ProcessFrame (tracking off: pose := gtC2wPoses[framesProcessed]; Coerce())
     def ProcessFrame(self, rgb_u8, depth_mm_i16, gt_c2w):
         """rgb_u8: uint8 [H,W,4] device tensor (uchar4, as ITMUChar4Image; [H,W,3] is padded with a copy);
         depth_mm_i16: int16 [H,W] millimetres; gt_c2w 4x4.  The kernels read both tensors in place (the reference
-        uploads the pre-converted ITM images every frame, ITMViewBuilder_CUDA.cu:61-62)."""
-        if rgb_u8.shape[-1] == 3:
-            rgb_u8 = torch.cat([rgb_u8, torch.full_like(rgb_u8[..., :1], 255)], -1)
-        assert rgb_u8.is_contiguous() and depth_mm_i16.is_contiguous()
-        self._frame_inputs = (rgb_u8, depth_mm_i16)  # keep alive while kernels may read them
-        self.state.rgb = rgb_u8.data_ptr()
+        uploads the pre-converted ITM images every frame, ITMViewBuilder_CUDA.cu:61-62).
+        With calib=: rgb_u8 is of the COLOUR camera's size and is copied into a buffer of the engine's own; depth_mm_i16 is the
+        raw image in the calibration's unit."""
+        self._take_inputs(rgb_u8, depth_mm_i16)
         M, invM = pose_from_c2w(gt_c2w)
-        if self.use_bilateral_filter:   # the filtered depth is in place: the rest of gps_tsdf_process_frame_fwd at the given pose
-            self._filter_depth(depth_mm_i16)
+        if self._converts_ahead():   # the view's depth is in place: the rest of gps_tsdf_process_frame_fwd at the given pose
+            self._convert_ahead(depth_mm_i16)
             self.track_state.pose_M[:] = M.tolist(); self.track_state.pose_invM[:] = invM.tolist()
-            check(lib.gps_tsdf_frame_map_fwd(C.byref(self.state), C.byref(self.track_state), 1, 0, self._forward_block(),
-                                             1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_frame_map_fwd")
-            self.camPoses.append((M, invM))
-            self.frames_processed += 1
-            return M, invM
-        # (gps_tsdf_process_frame's launches; Prepare keeps the point cloud's age and pose, and forward-renders if asked to)
-        check(lib.gps_tsdf_process_frame_fwd(C.byref(self.state), depth_mm_i16.data_ptr(), M.ctypes.data, invM.ctypes.data,
-                                             C.byref(self.track_state), self._forward_block(),
-                                             1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_process_frame_fwd")
+            self._map_half()
+        else:
+            # (gps_tsdf_process_frame's launches; Prepare keeps the point cloud's age and pose, and forward-renders if asked to)
+            check(lib.gps_tsdf_process_frame_fwd(C.byref(self.state), depth_mm_i16.data_ptr(), M.ctypes.data, invM.ctypes.data,
+                                                 C.byref(self.track_state), self._forward_block(),
+                                                 1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_process_frame_fwd")
         self.camPoses.append((M, invM))
         self.frames_processed += 1
         return M, invM
@@ -230,18 +293,13 @@ class TsdfEngine:
     def ProcessFrameTracked(self, rgb_u8, depth_mm_i16):
         """-> (M, invM) estimated by the tracker (ORUtils layout, numpy float32[16]).  Host-synchronous (see
         gps_tsdf_track_camera)."""
-        if rgb_u8.shape[-1] == 3:
-            rgb_u8 = torch.cat([rgb_u8, torch.full_like(rgb_u8[..., :1], 255)], -1)
-        assert rgb_u8.is_contiguous() and depth_mm_i16.is_contiguous()
-        self._frame_inputs = (rgb_u8, depth_mm_i16)
-        self.state.rgb = rgb_u8.data_ptr()
-        if self.use_bilateral_filter:   # the two halves again, the tracker reading the filtered depth (depth_mm NULL)
-            self._filter_depth(depth_mm_i16)
+        self._take_inputs(rgb_u8, depth_mm_i16)
+        if self._converts_ahead():   # convert first; the tracker reads the depth in place (depth_mm NULL); then the map half
+            self._convert_ahead(depth_mm_i16)
             check(lib.gps_tsdf_frame_track(C.byref(self.state), None, C.byref(self.track_cfg),
                                            C.byref(self.track_state), self.track_scratch.data_ptr(), self.track_scratch.numel(),
                                            self._stream()), "gps_tsdf_frame_track")
-            check(lib.gps_tsdf_frame_map_fwd(C.byref(self.state), C.byref(self.track_state), 1, 0, self._forward_block(),
-                                             1 if self.use_approximate_raycast else 0, self._stream()), "gps_tsdf_frame_map_fwd")
+            self._map_half()
         elif self.use_approximate_raycast:   # the two halves of gps_tsdf_process_frame_tracked, Prepare with the forward render
             check(lib.gps_tsdf_frame_track(C.byref(self.state), depth_mm_i16.data_ptr(), C.byref(self.track_cfg),
                                            C.byref(self.track_state), self.track_scratch.data_ptr(), self.track_scratch.numel(),
@@ -356,8 +414,8 @@ class TsdfEngine:
             return None
         W, H, P = self.W, self.H, self.W * self.H
         new = lambda: torch.zeros((H, W, 4), dtype=torch.uint8, device=self.device)
-        if t == InfiniTAM_IMAGE_ORIGINAL_RGB:
-            return self._frame_inputs[0].view(H, W, 4).clone()
+        if t == InfiniTAM_IMAGE_ORIGINAL_RGB:   # at the colour camera's size (out->ChangeDims(view->rgb->noDims), ITMBasicEngine.tpp:403)
+            return self._frame_inputs[0].view(self.H_rgb, self.W_rgb, 4).clone()
         if t == InfiniTAM_IMAGE_ORIGINAL_DEPTH:
             if getattr(self, "_depth_scratch", None) is None:
                 self._depth_scratch = torch.zeros(int(lib.gps_tsdf_depth_to_rgba8_scratch_bytes()), dtype=torch.uint8, device=self.device)

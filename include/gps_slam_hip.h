@@ -1227,6 +1227,57 @@ GPS_API int gps_tsdf_get_image(const gps_tsdf_state *s, const float *M, const fl
 GPS_API int64_t gps_tsdf_filter_scratch_bytes(int width, int height);
 GPS_API int gps_tsdf_convert_filter_depth(const gps_tsdf_state *s, const int16_t *depth_mm, void *scratch, gps_stream stream);
 
+/* ---- full RGB-D calibration (ITMRGBDCalib): a depth calibration, a colour camera of its own ----
+ * Off unless asked for: none of the entry points above changes, and a frame without these calls issues the launches it always
+ * issued.  A calibrated frame rides the path of the bilateral filter: convert first (gps_tsdf_convert_depth_calib or
+ * gps_tsdf_convert_filter_depth_calib), then gps_tsdf_frame_track with depth_mm == NULL, then gps_tsdf_frame_map_rgb. */
+enum gps_depth_calib_type {           /* ITMDisparityCalib::TrafoType */
+    GPS_DEPTH_CALIB_KINECT = 0,       /* t = a - raw; depth = t == 0 ? 0 : ((8 * b) * fx_d) / t; <= 0 (or NaN): -1 */
+    GPS_DEPTH_CALIB_AFFINE = 1        /* raw <= 0 ? -1 : raw * a + b  (a multiply, then an add) */
+};
+typedef struct {
+    int32_t type;                     /* gps_depth_calib_type */
+    float a, b;                       /* ITMDisparityCalib::GetParams(); the standard calibration is AFFINE, 1.0f / 1000.0f, 0 */
+} gps_depth_calib;
+typedef struct {
+    int32_t width, height;            /* of the colour image (may differ from the depth image's) */
+    float fx, fy, cx, cy;             /* intrinsics_rgb.projectionParamsSimple */
+    float depth_to_rgb[16];           /* trafo_rgb_to_depth.calib_inv, ORUtils layout m[col * 4 + row]: depth camera -> colour camera */
+    const uint8_t *rgb;               /* device, uchar4[height * width], 4-byte aligned */
+} gps_colour_camera;
+/* UpdateView's conversion (ITMViewBuilder_CPU.cpp:41-48; ITMViewBuilder_Shared.h:8-36): raw int16[H*W] (device) -> s->depth in
+ * the reference's float operation order; the Kinect type reads s->fx.  The standard calibration gives gps_tsdf_convert_depth's
+ * image bit for bit.  Reads of the state: width, height, fx, depth.  One launch.
+ * gps_tsdf_convert_filter_depth_calib: the same conversion into s->depth, then gps_tsdf_convert_filter_depth's five passes
+ * s->depth -> scratch -> ... -> s->depth (six launches; scratch as for gps_tsdf_convert_filter_depth).
+ * GPS_ERR_ARG before any launch: a NULL or misaligned pointer, a size <= 0, an unknown type, a Kinect calibration with a == 0 and
+ * b == 0 (the reference and the host layers turn that one into the standard calibration before it gets here). */
+GPS_API int gps_tsdf_convert_depth_calib(const gps_tsdf_state *s, const int16_t *raw, const gps_depth_calib *calib, gps_stream stream);
+GPS_API int gps_tsdf_convert_filter_depth_calib(const gps_tsdf_state *s, const int16_t *raw, const gps_depth_calib *calib, void *scratch,
+                                                gps_stream stream);
+/* M_rgb = calib_inv * M_d in ORUtils' Matrix4 * Matrix4 order, in float on the host (no device work). */
+GPS_API int gps_rgbd_m_rgb(const float *depth_to_rgb, const float *M_d, float *M_rgb);
+/* gps_tsdf_integrate with a colour camera of its own (IntegrateIntoScene, CPU.tpp:55-69; computeUpdatedVoxelColorInfo,
+ * Shared.h:106-140): depth, weight and the choice of the voxels that take colour are gps_tsdf_integrate's; such a voxel is
+ * projected with M_rgb and cam's intrinsics (plain IEEE divisions) and keeps clr and w_color when the point falls outside
+ * [1, width-2] x [1, height-2] of the colour image; otherwise four taps of cam->rgb at ITS width and the running mean.
+ * s->rgb is not read (it must still be a valid pointer).  The reference does not test pt_camera.z there: a negative z is
+ * reproduced; a NaN coordinate (0 / 0), which passes the reference's comparisons into a read outside the image, is dropped.
+ * One launch.  GPS_ERR_ARG before it: NULL pointers, an invalid state, a colour size <= 0, a misaligned image. */
+GPS_API int gps_tsdf_integrate_rgb(const gps_tsdf_state *s, const float *M, const gps_colour_camera *cam, gps_stream stream);
+/* gps_tsdf_frame_map_fwd with an optional colour camera: cam == NULL is exactly that call; otherwise the integration is
+ * gps_tsdf_integrate_rgb (fuse != 0) and everything else is unchanged. */
+GPS_API int gps_tsdf_frame_map_rgb(const gps_tsdf_state *s, gps_track_state *ts, int fuse, int reset_visible, void *fwd_block,
+                                   int use_approximate_raycast, const gps_colour_camera *cam, gps_stream stream);
+/* Colour registered to the depth camera -- OURS, not the reference's (the bridge for the splat half and the one-camera
+ * pipeline, which need colour in the depth camera's frame).  For every depth pixel with s->depth > 0: unproject with the depth
+ * intrinsics (z * ((x - cx) / fx)), transform with depth_to_rgb, project with the colour intrinsics, and, when z > 0 and the
+ * point lies in [1, width-2] x [1, height-2] of the colour image, take interpolateBilinear's sample (ITMPixelUtils.h:13-29,
+ * rounded to nearest as TO_UCHAR3 does) -> out uchar4[H*W] of the DEPTH size with alpha 255; every other pixel is 0 0 0 0.
+ * No occlusion test: a per-depth-pixel lookup, as sensor SDKs register colour.  Reads of the state: width, height, fx, fy, cx, cy,
+ * depth.  One launch, no host read.  GPS_ERR_ARG before it as above (out: 4-byte aligned). */
+GPS_API int gps_tsdf_register_colour(const gps_tsdf_state *s, const gps_colour_camera *cam, uint8_t *out_rgba8, gps_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
