@@ -677,7 +677,12 @@ def test_fused_adam_is_bit_identical_to_separate_step_under_the_wide_camera(N):
     _fused_adam_against_separate_step(N, W, H, g, case.vm, case.K, case.cam_pos)
 
 
-def _fused_adam_against_separate_step(N, W, H, g, vm, K, cam_pos):
+def _fused_adam_against_separate_step(N, W, H, g, vm, K, cam_pos, deg=3, Ksh=16, after_step=None):
+    """deg: the SH degree in use -- one for three steps, or a sequence with the degree of every step (one Adam state throughout, as
+    under the SH schedule); Ksh: the coefficients per Gaussian (g["sh"] is [N, Ksh, 3], Ksh > 1);
+    after_step(fuse_small, step, deg, P0, A, mA, vA): called once the step's parameters and moments have been compared."""
+    assert g["sh"].shape[1] == Ksh and Ksh > 1
+    degs = [deg] * 3 if isinstance(deg, int) else list(deg)
     import ctypes as C
     from gps_slam_amd import gsplat_ops as ops
     from gps_slam_amd._lib import AdamSegment, check, lib
@@ -698,11 +703,11 @@ def _fused_adam_against_separate_step(N, W, H, g, vm, K, cam_pos):
         mA, vA = {k: torch.zeros_like(v) for k, v in A.items()}, {k: torch.zeros_like(v) for k, v in A.items()}
         mB, vB = {k: torch.zeros_like(v) for k, v in B.items()}, {k: torch.zeros_like(v) for k, v in B.items()}
         stepped = names if fuse_small else ("rest",)
-        for step in (1, 2, 3):
+        for step, deg in enumerate(degs, 1):
             # the projected state both paths consume (parameters move every step when the small tensors are stepped)
             radii, m2, depths, conics, colors, opac = ops.gauss_preprocess_fwd(A["means"], A["ls"], A["q"], A["ol"], A["dc"],
-                                                                              A["rest"], 3, vmT, KT, cp, W, H)
-            gA = ops.gauss_preprocess_bwd(A["means"], A["ls"], A["q"], A["ol"], A["dc"], A["rest"], 3, vmT, KT, cp, W, H, 0.3,
+                                                                              A["rest"], deg, vmT, KT, cp, W, H)
+            gA = ops.gauss_preprocess_bwd(A["means"], A["ls"], A["q"], A["ol"], A["dc"], A["rest"], deg, vmT, KT, cp, W, H, 0.3,
                                           radii, conics, v_m2, v_con, v_col, v_op)
             gmap = dict(means=gA[0], ls=gA[1], q=gA[2], ol=gA[3], dc=gA[4], rest=gA[5])
             ops.adam_step([A[k] for k in stepped], [gmap[k] for k in stepped], [mA[k] for k in stepped],
@@ -717,7 +722,7 @@ def _fused_adam_against_separate_step(N, W, H, g, vm, K, cam_pos):
                     small[j].param, small[j].exp_avg, small[j].exp_avg_sq = B[k].data_ptr(), mB[k].data_ptr(), vB[k].data_ptr()
                     small[j].numel, small[j].lr = B[k].numel(), lrs[k]
             og = [p(x) if want_g else None for x in outB]
-            check(lib.gps_gauss_preprocess_bwd_adam(N, 16, 3, p(B["means"]), p(B["ls"]), p(B["q"]), p(B["ol"]), p(B["dc"]),
+            check(lib.gps_gauss_preprocess_bwd_adam(N, Ksh, deg, p(B["means"]), p(B["ls"]), p(B["q"]), p(B["ol"]), p(B["dc"]),
                                                     p(B["rest"]), p(vmT), p(KT), p(cp), W, H, 0.3, p(radii), p(conics), p(v_m2),
                                                     p(v_con), p(v_col), p(v_op), og[0], og[1], og[2], og[3], og[4],
                                                     p(g_restB) if step == 2 else None, p(mB["rest"]), p(vB["rest"]), lrs["rest"],
@@ -730,8 +735,13 @@ def _fused_adam_against_separate_step(N, W, H, g, vm, K, cam_pos):
                     assert torch.equal(a, b)
             if step == 2:
                 assert torch.equal(g_restB, gA[5])
+            if after_step is not None:
+                after_step(fuse_small, step, deg, P0, A, mA, vA)
         for k in stepped:
-            assert (A[k] != P0[k]).any(), k
+            if k == "rest" and max(degs) == 0:   # degree 0 never reaches sh_rest: zero gradient, zero moments, not one bit moves
+                assert torch.equal(A[k], P0[k]) and not mA[k].any() and not vA[k].any()
+            else:
+                assert (A[k] != P0[k]).any(), k
 
 
 def test_hip_chain_matches_committed_splat_golden():

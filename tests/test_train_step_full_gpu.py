@@ -28,6 +28,7 @@ import pytest
 import torch
 
 from tests import scenes
+from tests.degree_cases import oracle_preprocess as _oracle_preprocess, oracle_preprocess_bwd as _oracle_preprocess_bwd  # (the one copy)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -64,40 +65,6 @@ def _build(N, W, H, scale_range, seed, strips=True, intr=None):
     ref[torch.rand((H, W, 1), generator=gen).to(DEV) < 0.1] = 0.0  # raycast misses -> clamped to 1000
     cam = Camera(0, W, H, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), c2w, image=gt, device=DEV)
     return models, cam, ref, base, gt, c2w, K
-
-
-def _oracle_preprocess(P, vm, K, cam_pos, W, H, max_radii=100, deg=3):
-    """RawGaussianModel::gesForward up to the binning (raw_gs_model.cpp:207-286) with the oracle operators."""
-    from oracle import splat_ref as orc
-    means, ls, quats, dc, rest, ol = P
-    scales = np.exp(ls)
-    radii, m2, depths, conics = orc.proj_fwd(means, quats, scales, vm, K, W, H)
-    radii = np.minimum(radii, max_radii)
-    dirs = means - cam_pos[None]
-    sh = np.concatenate([dc[:, None], rest], 1)
-    rgb = np.maximum(orc.sh_fwd(deg, dirs, sh, radii > 0) + np.float32(0.5), np.float32(0.0))
-    colors = np.concatenate([rgb, depths[:, None]], 1).astype(np.float32)
-    opac = (np.float32(1.0) / (np.float32(1.0) + np.exp(-ol[:, 0]))).astype(np.float32)
-    return radii, m2, depths, conics, colors, opac, scales, dirs, sh
-
-
-def _oracle_preprocess_bwd(P, vm, K, cam_pos, W, H, radii, conics, v_m2, v_con, v_col, v_op, deg=3):
-    """adjoint of the chain above: clamp_min mask -> SH bwd (v_dirs -> v_means) -> projection bwd -> exp / sigmoid."""
-    from oracle import splat_ref as orc
-    means, ls, quats, dc, rest, ol = P
-    scales = np.exp(ls)
-    dirs = means - cam_pos[None]
-    sh = np.concatenate([dc[:, None], rest], 1)
-    vis = radii > 0
-    raw = orc.sh_fwd(deg, dirs, sh, vis) + np.float32(0.5)
-    v_rgb = np.where(raw >= 0, v_col[:, :3], 0).astype(np.float32)
-    v_sh, v_dirs = orc.sh_bwd(deg, dirs, sh, vis, v_rgb)
-    v_means, v_quats, v_scales = orc.proj_bwd(means, quats, scales, vm, K, W, H, radii, conics, v_m2,
-                                              np.ascontiguousarray(v_col[:, 3]), v_con)
-    v_means = v_means + v_dirs
-    o = 1.0 / (1.0 + np.exp(-ol[:, 0].astype(np.float64)))
-    v_ol = (v_op.astype(np.float64) * o * (1 - o)).astype(np.float32)[:, None]
-    return v_means, (v_scales * scales).astype(np.float32), v_quats, v_sh[:, 0], v_sh[:, 1:], v_ol
 
 
 def _row_rel(got, ref, vis):
